@@ -20,18 +20,26 @@ The default workload ("rdo") is the metric's "fwd_txfm+quant+SAD" loop:
 by default side by side: the legs are independent (the residual is given),
 so C3 runs on a second stream beside C2 -- C3 is bound by the vector-memory
 address path, C2 by HBM writes -- which shortens the step ~10 % (measured
-0.967 -> 0.872 ms).  The per-kernel roofline and legs_ms come from a serial
-pass after the timed region (isolated legs); legs_overlapped_ms keeps the
-stretched spans of the timed region.  --serial times the legs back to back
-on one stream; --workload c2 / c3 times one leg alone.
+0.967 -> 0.872 ms).  --serial times the legs back to back on one stream;
+--workload c2 / c3 times one leg alone.
+
+A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms up, times the N
+steps and prints the result line (value, ms_per_step, the configuration and
+legs_overlapped_ms, the legs' stretched spans inside the timed region).
+--dump-outputs DIR also writes what the last timed step computed (see
+dump_outputs).  --full adds everything that takes runs of its own: the
+per-kernel roofline and legs_ms from a serial pass after the timed region
+(isolated legs), the `c3` figures, the `c4` (and at N > 1 `c5`) sub-objects
+and the CPU baselines.
 
 Multi-GPU: one process per GPU (torchrun), each rank processes its own frame
 (independent units, no data-path collective): weak scaling.  Timing: barrier +
 device sync on both sides of exactly `--steps` steps, max over ranks.
 
-Extra fields: `roofline` for the dominant kernel (algorithmic bytes / average
-launch duration, from HIP events on the launch stream) and `cpu_baseline`
-(the oracle's C restatement on the host cores, rank 0 at N=1, bounded sample).
+Extra fields with --full: `roofline` for the dominant kernel (algorithmic
+bytes / average launch duration, from HIP events on the launch stream) and
+`cpu_baseline` (the oracle's C restatement on the host cores, rank 0 at N=1,
+bounded sample).
 """
 import argparse
 import ctypes
@@ -131,7 +139,22 @@ def parse():
                     help="1: C4's per-size kernels all on the caller's stream (isolated "
                          "per-kernel timings under a profiler; lavish_set_fan_width)")
     ap.add_argument("--pmc-json", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: the CPU baselines, the "
+                         "isolated-leg pass with its roofline and C3 figures, the c4 / c5 "
+                         "sub-objects of the default line (a plain run sets up, warms up, times "
+                         "--steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy "
+                         "(workloads rdo, c2, c3, c3sub; a fixed seeded sample of the large "
+                         "arrays, see dump_outputs)")
+    args = ap.parse_args()
+    if args.dump_outputs and args.workload not in ("rdo", "c2", "c3", "c3sub"):
+        ap.error("--dump-outputs covers the workloads rdo, c2, c3 and c3sub, not %s"
+                 % args.workload)
+    # the CPU baselines belong to --full (and --no-cpu still drops them there)
+    args.cpu = args.full and not args.no_cpu
+    return args
 
 
 def host_cores():
@@ -781,7 +804,7 @@ def main_c4(args):
         if rv is not None:
             line["hbm_roofline"] = line["roofline"]
             line["roofline"] = rv
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.cpu:
         line["cpu_baseline"] = cpu_baseline_c4(args)
     if rank == 0:
         print(json.dumps(line), flush=True)
@@ -930,7 +953,7 @@ def main_inter(args):
                      "algorithmic_bytes_per_launch": nbytes},
     }
     line["roofline"]["frac"] = round(line["roofline"]["achieved"] / HBM_PEAK_GBS, 4)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.cpu:
         line["cpu_baseline"] = cpu_baseline_inter(args)
     if rank == 0:
         print(json.dumps(line), flush=True)
@@ -1085,7 +1108,7 @@ def main_pixel(args):
                              "exceed the HBM bytes"},
     }
     line["roofline"]["frac"] = round(line["roofline"]["achieved"] / HBM_PEAK_GBS, 4)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.cpu:
         line["cpu_baseline"] = cpu_baseline_pixel(args)
     if rank == 0:
         print(json.dumps(line), flush=True)
@@ -1291,7 +1314,7 @@ def main_scale(args):
                                    len(jobs_np)),
                        kernel="scale_kernel<u8, 8, 8> (lavish_convolve_2d_scale_batch)",
                        nbytes=scale_bytes(W, H, args.refs, len(jobs_np)))
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.cpu:
         line["cpu_baseline"] = cpu_baseline_scale(args)
     if rank == 0:
         print(json.dumps(line), flush=True)
@@ -1400,7 +1423,7 @@ def main_mesh(args):
     r["note"] = ("algorithmic bytes = jobs x %d nominal mesh candidates (unclamped) x 256 B "
                  "of candidate rows read by the SADs; the NSTEP walk's own reads not counted; "
                  "frac against the HBM peak for scale only" % cand)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.cpu:
         line["cpu_baseline"] = cpu_baseline_mesh(args)
     if rank == 0:
         print(json.dumps(line), flush=True)
@@ -1535,7 +1558,7 @@ def main_warp(args):
                      "algorithmic_bytes_per_launch": nbytes},
     }
     line["roofline"]["frac"] = round(line["roofline"]["achieved"] / HBM_PEAK_GBS, 4)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.cpu:
         line["cpu_baseline"] = cpu_baseline_warp(args)
     if rank == 0:
         print(json.dumps(line), flush=True)
@@ -1707,7 +1730,7 @@ def main_compound(args):
                      "algorithmic_bytes_per_launch": nbytes // 2},
     }
     line["roofline"]["frac"] = round(line["roofline"]["achieved"] / HBM_PEAK_GBS, 4)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.cpu:
         line["cpu_baseline"] = cpu_baseline_compound(args)
     if rank == 0:
         print(json.dumps(line), flush=True)
@@ -1908,7 +1931,7 @@ def main_tpl(args):
                               "achieved_GBps": round(blk_bytes / (legs[3] * 1e-3) / 1e9, 1)}},
     }
     line["roofline"]["frac"] = round(line["roofline"]["achieved"] / HBM_PEAK_GBS, 4)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.cpu:
         line["cpu_baseline"] = cpu_baseline_tpl(args)
     if rank == 0:
         print(json.dumps(line), flush=True)
@@ -2055,7 +2078,7 @@ def main_rate(args):
         "cost_coeffs": cc,
     }
     line["roofline"]["frac"] = round(line["roofline"]["achieved"] / HBM_PEAK_GBS, 4)
-    if not args.no_cpu:
+    if args.cpu:
         line["cpu_baseline"] = cpu_baseline_rate(args)
     print(json.dumps(line), flush=True)
 
@@ -2198,6 +2221,75 @@ class RdoStep:
             ev[5].record(stream)
 
 
+DUMP_SEED = 20240  # of the sampled block / job indices; fixed, so two builds dump the same ones
+DUMP_COEFF_VALUES = 100000   # per qcoeff / dqcoeff array (float64: 0.8 MB, 28 arrays)
+DUMP_EOB_VALUES = 500000     # per eob array (float32: 2 MB, 14 arrays)
+DUMP_JOBS = 100000           # rows of the C3 arrays (float64, 5 columns each)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def _dump_sample(n, cap, rng):
+    """All of range(n), or a sorted seeded sample of `cap` of them."""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(rng.choice(n, size=cap, replace=False))
+
+
+def dump_outputs(R, out_dir):
+    """--dump-outputs: what RdoStep.step left in its output tensors, i.e. what
+    a caller of the timed path receives, as out_dir/<name>.npy.  The integer
+    outputs are stored exactly: coefficients and the search's records as
+    float64, eobs (<= 1024) as float32.  The full C2 output of a 1080p frame
+    is ~2.5 GB, so per TX size a seeded sample of blocks is kept (every type
+    of a sampled block); the caps above bound the files at 64 MB for any
+    frame size.
+
+      c2_<size>_qcoeff / _dqcoeff  [type slot, sampled block, coefficient]
+      c2_<size>_eob                [type slot, sampled block]
+      c3_results      [job, (best_row, best_col, bestsme, steps, searches)]
+      c3_cost_list    [job, 5]
+      c3_subpel       [job, (best_row, best_col, besterr, distortion, sse)]  (c3sub)
+
+    Returns {name: the block / job indices of its sampled axis}."""
+    import torch
+    L, M = R.L, R.M
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    rng = np.random.default_rng(DUMP_SEED)
+    total = 0
+    picked = {}
+
+    def save(name, a, idx):
+        nonlocal total
+        total += a.nbytes
+        picked[name] = idx
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+    def rows(t, idx):  # t[:, idx] on the device, then to the host
+        return t.index_select(1, torch.from_numpy(idx).to(t.device)).cpu().numpy()
+
+    def fields(rec):  # a structured array as float64 columns
+        return np.stack([rec[f].astype(np.float64) for f in rec.dtype.names], axis=1)
+
+    if R.do_c2:
+        for s in R.sizes:
+            o = R.frame.outs[s]
+            nt, nb, n = o["qcoeff"].shape
+            idx = _dump_sample(nb, max(1, DUMP_COEFF_VALUES // (nt * n)), rng)
+            for k in ("qcoeff", "dqcoeff"):
+                save("c2_%s_%s" % (L.TX_SIZES[s], k), rows(o[k], idx).astype(np.float64), idx)
+            idx = _dump_sample(nb, max(1, DUMP_EOB_VALUES // nt), rng)
+            save("c2_%s_eob" % L.TX_SIZES[s], rows(o["eob"], idx).astype(np.float32), idx)
+    if R.do_c3:
+        idx = _dump_sample(len(R.jobs_np), DUMP_JOBS, rng)
+        save("c3_results", fields(M.results_numpy(R.c3_out)[idx]), idx)
+        save("c3_cost_list", R.c3_cl.cpu().numpy()[idx].astype(np.float64), idx)
+        if R.do_sub:
+            save("c3_subpel", fields(M.subpel_results_numpy(R.sub_out)[idx]), idx)
+    assert total <= DUMP_MAX_BYTES, total
+    return picked
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
@@ -2326,21 +2418,29 @@ def main():
     if status[0] != 0:
         raise RuntimeError("HIP error during bench: %s" % (status,))
     K = args.steps
+    if args.dump_outputs:
+        # the timed region's last step, before anything below reuses the buffers
+        dump_outputs(R, args.dump_outputs if world == 1
+                     else os.path.join(args.dump_outputs, "rank%d" % rank))
     step_ms = sum(ev[k][0].elapsed_time(ev[k][5]) for k in range(K)) / K
     c3_ms = sum(ev[k][1].elapsed_time(ev[k][2]) for k in range(K)) / K if do_c3 else 0.0
     c2_ms = sum(ev[k][3].elapsed_time(ev[k][4]) for k in range(K)) / K if do_c2 else 0.0
+    # the per-kernel figures (roofline, legs_ms, c3) need each leg alone: as
+    # timed when the legs run back to back, else from --full's serial pass
+    detail = args.full or not overlap
     # the C3 results the timed region produced (its last step): the serial
     # pass below overwrites the output buffer
-    c3_res = M.results_numpy(R.c3_out) if do_c3 else None
+    c3_res = M.results_numpy(R.c3_out) if do_c3 and detail else None
     legs_overlapped = None
     if overlap:
-        # the legs share the GPU in the timed region, which stretches each; the
-        # per-kernel roofline is taken from a serial pass after it (isolated
-        # legs, same inputs), not from the overlapped leg spans
         legs_overlapped = ({"c2_c3_fused_launch": round(c2_ms, 4)} if R.fused else
                            {"c2_txq_frame_le16pt": round(c2_ms, 4),
                             "c3_diamond_then_c2_32pt": round(c3_ms, 4)} if R.split32 else
                            {"c2_txq_frame": round(c2_ms, 4), "c3_diamond": round(c3_ms, 4)})
+    if overlap and args.full:
+        # the legs share the GPU in the timed region, which stretches each; the
+        # per-kernel roofline is taken from a serial pass after it (isolated
+        # legs, same inputs), not from the overlapped leg spans
         KS = max(5, K // 2)
         evs = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(6)) for _ in range(KS)]
         step(ovl=False)
@@ -2349,37 +2449,38 @@ def main():
         torch.cuda.synchronize()
         c3_ms = sum(evs[k][1].elapsed_time(evs[k][2]) for k in range(KS)) / KS
         c2_ms = sum(evs[k][3].elapsed_time(evs[k][4]) for k in range(KS)) / KS
-    c2_bytes = sum(algorithmic_bytes(L, s, W, H) for s in sizes)
-    # + the tiled copy of the references: read once, written at 2x
-    c3_bytes = c3_algorithmic_bytes(c3_res, len(jobs_np), C3_BLOCK, C3_BLOCK, C3_SKIP, C3_CL) \
-        + R.trefs.numel() + R.c3_tiles.data.numel() if do_c3 else 0
+    if detail:
+        c2_bytes = sum(algorithmic_bytes(L, s, W, H) for s in sizes)
+        # + the tiled copy of the references: read once, written at 2x
+        c3_bytes = c3_algorithmic_bytes(c3_res, len(jobs_np), C3_BLOCK, C3_BLOCK, C3_SKIP, C3_CL) \
+            + R.trefs.numel() + R.c3_tiles.data.numel() if do_c3 else 0
 
-    traffic = c3_hbm = traffic_src = None
-    if os.path.exists(args.pmc_json):
-        try:
-            pj = json.load(open(args.pmc_json))
-            traffic = pj.get("frame_hbm_bytes_per_launch")
-            c3_hbm = pj.get("diamond_hbm_bytes_per_launch")
-            traffic_src = "%s (round %s: %s)" % (os.path.relpath(args.pmc_json, ROOT),
-                                                  pj.get("round"), pj.get("command", ""))
-        except (ValueError, OSError):
-            traffic = None
+        traffic = c3_hbm = traffic_src = None
+        if os.path.exists(args.pmc_json):
+            try:
+                pj = json.load(open(args.pmc_json))
+                traffic = pj.get("frame_hbm_bytes_per_launch")
+                c3_hbm = pj.get("diamond_hbm_bytes_per_launch")
+                traffic_src = "%s (round %s: %s)" % (os.path.relpath(args.pmc_json, ROOT),
+                                                      pj.get("round"), pj.get("command", ""))
+            except (ValueError, OSError):
+                traffic = None
 
-    # dominant kernel: the longer leg
-    if do_c2 and (c2_ms >= c3_ms):
-        roof = {"bound": "hbm",
-                "kernel": "lavish_txq_frame (txq_multi_kernel<0> + <1>: one launch per VGPR class, 14 sizes)",
-                "achieved": round(c2_bytes / (c2_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "traffic": traffic, "traffic_source": traffic_src,
-                "avg_launch_ms": round(c2_ms, 4), "algorithmic_bytes_per_launch": c2_bytes}
-    else:
-        roof = {"bound": "hbm",
-                "kernel": "ref_tiles_kernel + diamond_kernel<16,16,false,true> "
-                          "(lavish_ref_tiles_build + lavish_full_pixel_search_batch_tiled)",
-                "achieved": round(c3_bytes / (c3_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS,
-                "unit": "GB/s", "traffic": None, "avg_launch_ms": round(c3_ms, 4),
-                "algorithmic_bytes_per_launch": c3_bytes}
-    roof["frac"] = round(roof["achieved"] / HBM_PEAK_GBS, 4)
+        # dominant kernel: the longer leg
+        if do_c2 and (c2_ms >= c3_ms):
+            roof = {"bound": "hbm",
+                    "kernel": "lavish_txq_frame (txq_multi_kernel<0> + <1>: one launch per VGPR class, 14 sizes)",
+                    "achieved": round(c2_bytes / (c2_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "traffic": traffic, "traffic_source": traffic_src,
+                    "avg_launch_ms": round(c2_ms, 4), "algorithmic_bytes_per_launch": c2_bytes}
+        else:
+            roof = {"bound": "hbm",
+                    "kernel": "ref_tiles_kernel + diamond_kernel<16,16,false,true> "
+                              "(lavish_ref_tiles_build + lavish_full_pixel_search_batch_tiled)",
+                    "achieved": round(c3_bytes / (c3_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS,
+                    "unit": "GB/s", "traffic": None, "avg_launch_ms": round(c3_ms, 4),
+                    "algorithmic_bytes_per_launch": c3_bytes}
+        roof["frac"] = round(roof["achieved"] / HBM_PEAK_GBS, 4)
 
     sb = sb64_count(W, H)
     value = world * sb * args.steps / elapsed
@@ -2421,15 +2522,18 @@ def main():
                       % args.c3_wg_cap if args.c3_wg_cap else
                       "C3 on a second stream beside C2")) if overlap else "C3 then C2, one stream",
         },
-        "roofline": roof,
-        "legs_ms": {"c2_txq_frame": round(c2_ms, 4), "c3_diamond": round(c3_ms, 4),
-                    "step_event_ms": round(step_ms, 4),
-                    "legs": "isolated (serial pass after the timed region)" if overlap
-                            else "as timed"},
     }
+    if detail:
+        line["roofline"] = roof
+        line["legs_ms"] = {"c2_txq_frame": round(c2_ms, 4), "c3_diamond": round(c3_ms, 4),
+                           "step_event_ms": round(step_ms, 4),
+                           "legs": "isolated (serial pass after the timed region)" if overlap
+                                   else "as timed"}
+    else:  # the isolated legs and their roofline take --full's serial pass
+        line["legs_ms"] = {"step_event_ms": round(step_ms, 4)}
     if legs_overlapped is not None:
         line["legs_overlapped_ms"] = legs_overlapped
-    if do_c3:
+    if do_c3 and detail:
         # the search's candidate re-reads are served by L2: its
         # algorithmic rate is not an HBM rate; the PMC bytes that reach HBM
         # (tiles + search + cost tables) stand beside it
@@ -2441,25 +2545,25 @@ def main():
                       "hbm_bytes_pmc": c3_hbm,
                       "hbm_GBps_pmc": round(c3_hbm / (c3_ms * 1e-3) / 1e9, 1) if c3_hbm else None,
                       "leg_ms": round(c3_ms, 4)}
-    if args.workload == "rdo" and not args.no_c4:
+    if args.workload == "rdo" and args.full and not args.no_c4:
         # the 4K 10-bit RDO configuration (BASELINE configs[3]), timed after
         # the headline region so the driver's run records it too
         roof4, line["c4"] = c4_leg(L, max(5, args.steps // 2), max(2, args.warmup),
                                    args.rdmult, args.qindex)
         line["c4"]["roofline"] = roof4
-        if rank == 0 and world == 1 and not args.no_cpu:
+        if rank == 0 and world == 1 and args.cpu:
             a4 = argparse.Namespace(**vars(args))
             a4.workload = "c4"
             a4.cpu_seconds = max(3.0, args.cpu_seconds / 2)
             line["c4"]["cpu_baseline"] = cpu_baseline_c4(a4)
-    if args.workload == "rdo" and world > 1 and not args.no_c4:
+    if args.workload == "rdo" and world > 1 and args.full and not args.no_c4:
         # the SB-row shard of north_star over RCCL (BASELINE configs[4]): at
         # N > 1 the driver's scaling run measures it from this object
         line["c5"] = c5_leg(L, max(5, args.steps // 2), max(2, args.warmup), args.rdmult,
                             args.qindex, world, rank,
                             c4_ms=line.get("c4", {}).get("ms_per_frame"),
                             form="band" if args.c5_form == "band" else "tiles")
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.cpu:
         line["cpu_baseline"] = cpu_baseline(args)
     if rank == 0:
         print(json.dumps(line), flush=True)

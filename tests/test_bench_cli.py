@@ -88,6 +88,45 @@ def _bench_module():
     return b
 
 
+def _parse(b, argv, monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    return b.parse()
+
+
+def test_full_is_off_by_default_and_owns_the_cpu_baselines(monkeypatch):
+    """A plain run does only the headline's work: --full is off, and the CPU
+    baselines run only under it (--no-cpu still drops them there)."""
+    b = _bench_module()
+    a = _parse(b, ["--gpus", "1", "--steps", "7", "--warmup", "2"], monkeypatch)
+    assert (a.full, a.cpu, a.steps, a.warmup, a.dump_outputs) == (False, False, 7, 2, None)
+    assert _parse(b, ["--full"], monkeypatch).cpu is True
+    assert _parse(b, ["--full", "--no-cpu"], monkeypatch).cpu is False
+    assert _parse(b, ["--no-cpu"], monkeypatch).cpu is False
+
+
+def test_dump_outputs_refuses_workloads_it_does_not_cover():
+    out = subprocess.run([sys.executable, BENCH, "--workload", "tpl", "--dump-outputs", "x",
+                          "--dry-run"], env=_env(), capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2
+    assert "--dump-outputs" in out.stderr
+
+
+def test_dump_sample_is_seeded_and_bounded():
+    """The sampled indices of --dump-outputs: all of a short axis, else a
+    sorted sample without repeats that the seed alone decides."""
+    import numpy as np
+    b = _bench_module()
+    assert b._dump_sample(5, 5, np.random.default_rng(1)).tolist() == [0, 1, 2, 3, 4]
+    x = b._dump_sample(1000, 37, np.random.default_rng(b.DUMP_SEED))
+    y = b._dump_sample(1000, 37, np.random.default_rng(b.DUMP_SEED))
+    assert x.tolist() == y.tolist() and len(x) == 37
+    assert (np.diff(x) > 0).all() and 0 <= x[0] and x[-1] < 1000
+    # the caps keep any frame's files under the limit: 14 sizes x (2 coefficient
+    # arrays + eob) + the three C3 arrays of 5 columns
+    worst = 14 * (2 * 8 * b.DUMP_COEFF_VALUES + 4 * b.DUMP_EOB_VALUES) + 3 * 5 * 8 * b.DUMP_JOBS
+    assert worst <= b.DUMP_MAX_BYTES
+
+
 def test_c4_counts_staleness_check():
     """bench.c4_roofline keeps profiles/c4_valu.json's issued-VALU / traffic
     fields only while every counted kernel still has the resource signature

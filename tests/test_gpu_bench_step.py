@@ -157,3 +157,63 @@ def test_search_workgroup_cap_sweep(step, c3_expected, cap, queued):
     finally:
         R.M.set_search_workgroup_cap(0)
         R.M.set_search_schedule(True)
+
+
+def test_dump_outputs_is_the_steps_outputs(step, tmp_path):
+    """bench.py --dump-outputs: the files hold, exactly, the rows of the step's
+    output tensors at the indices dump_outputs reports; float32 / float64
+    only, at most 64 MB, and the same files when dumped again."""
+    import torch
+    b, R = step
+    R.step()
+    torch.cuda.synchronize()
+    picked = b.dump_outputs(R, str(tmp_path / "a"))
+    again = b.dump_outputs(R, str(tmp_path / "b"))
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    want = ["c2_%s_%s.npy" % (R.L.TX_SIZES[s], k) for s in R.sizes
+            for k in ("qcoeff", "dqcoeff", "eob")] + ["c3_results.npy", "c3_cost_list.npy"]
+    assert names == sorted(want) and sorted(picked) == sorted(n[:-4] for n in want)
+    total = 0
+    for n in names:
+        a = np.load(tmp_path / "a" / n)
+        assert a.dtype in (np.float32, np.float64), n
+        total += a.nbytes
+        np.testing.assert_array_equal(a, np.load(tmp_path / "b" / n), err_msg=n)
+        np.testing.assert_array_equal(picked[n[:-4]], again[n[:-4]], err_msg=n)
+    assert total <= 64 << 20
+    for s in R.sizes:
+        for k in ("qcoeff", "dqcoeff", "eob"):
+            name = "c2_%s_%s" % (R.L.TX_SIZES[s], k)
+            full = R.frame.outs[s][k].cpu().numpy()
+            np.testing.assert_array_equal(np.load(tmp_path / "a" / (name + ".npy")),
+                                          full[:, picked[name]], err_msg=name)
+    res = R.M.results_numpy(R.c3_out)[picked["c3_results"]]
+    got = np.load(tmp_path / "a" / "c3_results.npy")
+    for i, f in enumerate(("best_row", "best_col", "bestsme", "steps", "searches")):
+        np.testing.assert_array_equal(got[:, i], res[f], err_msg=f)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "c3_cost_list.npy"),
+                                  R.c3_cl.cpu().numpy()[picked["c3_cost_list"]])
+
+
+def test_plain_run_is_lean(tmp_path):
+    """`bench.py --gpus 1 --steps N --warmup W` in a fresh process: N timed
+    steps, the headline fields, the dumped outputs -- and nothing of what
+    --full owns (CPU baselines, the serial pass's figures, c4)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1",
+                          "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "d")],
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert (line["steps"], line["warmup"], line["n_gpus"]) == (3, 1, 1)
+    assert line["unit"] == "SB64/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "int32" and line["metric"].startswith("superblocks/s")
+    # value = the frame's 510 SB64 per timed step
+    assert line["value"] == pytest.approx(510 / (line["ms_per_step"] * 1e-3), rel=1e-3)
+    for k in ("cpu_baseline", "c4", "c5", "c3", "roofline"):
+        assert k not in line, k
+    assert sorted(line["legs_ms"]) == ["step_event_ms"]
+    assert len(list((tmp_path / "d").glob("*.npy"))) == 14 * 3 + 2

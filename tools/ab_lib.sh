@@ -2,7 +2,8 @@
 # tools/ab_lib.sh TAG ALT_LIB ROUNDS BENCH_ARGS... -- A/B of two builds of the
 # library on one box: `bench.py BENCH_ARGS` alternately with the tree's
 # liblavish_hip.so and with ALT_LIB (LAVISH_HIP_LIB), ROUNDS times each;
-# prints each run's ms_per_step.  Stops at the first failing run.
+# prints each run's ms_per_step (and, with --full among BENCH_ARGS, the
+# isolated C2 leg and the roofline fraction).  Stops at the first failing run.
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
 TAG=$1; ALT=$2; N=$3; shift 3

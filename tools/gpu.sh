@@ -10,7 +10,8 @@
 #   test=EXPR             pytest -m gpu -k EXPR   (EXPR commas -> spaces)
 #   file=PATH             pytest -m gpu PATH
 #   smoke                 __graft_entry__.smoke()
-#   bench=ARGS            python bench.py ARGS; prints the line's summary
+#   bench=ARGS            python bench.py ARGS; prints the line's summary (its legs,
+#                         cpu and c4 columns need --full among ARGS)
 #   kt=NAME=ARGS          rocprofv3 --kernel-trace --stats of bench.py ARGS
 #   pmc=NAME=CTRS=ARGS    one rocprofv3 --pmc pass (CTRS comma-separated)
 #   traffic=NAME=ARGS     FETCH_SIZE and WRITE_SIZE passes of bench.py ARGS
