@@ -312,6 +312,81 @@ def test_ref_tiles_layout(stride, rows):
     np.testing.assert_array_equal(got.reshape(2, ns, fh, 32), exp)
 
 
+CAP_BORDER = 160
+
+
+@pytest.fixture(scope="module")
+def capped():
+    """A seeded 352x288 frame with 2 references: 792 16x16 jobs = 99 eight-job
+    wave units = 32 virtual workgroups of the tiled DIAMOND search, with the L1
+    mv cost.  Per use_downsampled_sad: the oracle's results and cost lists, and
+    the uncapped search's output bytes."""
+    import torch
+    import lavish_dsp.synth as synth
+    from lavish_dsp import motion as M
+    W, H, step_param = 352, 288, 1
+    src, refs = synth.motion_planes(W, H, 2, CAP_BORDER, seed=91)
+    stride = src.shape[1]
+    jobs = M.frame_jobs(W, H, stride, CAP_BORDER, src.size, 16, 16, refs.shape[0], (13, -21),
+                        (2, -3))
+    assert len(jobs) == 792
+    ts, tr = torch.from_numpy(src).cuda(), torch.from_numpy(refs).cuda()
+    tiles = M.RefTiles(tr, ts.stride(0)).build()
+    dj = M.to_device(jobs)
+    cost = M.l1_cost_params(1)
+    out = torch.empty(len(jobs) * M.RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    cl = torch.empty((len(jobs), 5), dtype=torch.int32, device="cuda")
+
+    def run(skip):
+        out.fill_(0x55)
+        cl.fill_(-7)
+        M.full_pixel_search_batch(ts, tr, 16, 16, dj, cost, "diamond", step_param, bool(skip),
+                                  True, out=out, cost_lists=cl, tiles=tiles)
+        torch.cuda.synchronize()
+        return out.cpu().numpy().copy(), cl.cpu().numpy().copy()
+
+    M.set_search_workgroup_cap(0)
+    M.set_search_schedule(True)
+    expected = {}
+    for skip in (0, 1):
+        dia = O.diamond_batch(src.reshape(-1), refs.reshape(-1), stride, 16, 16, jobs, step_param,
+                              1, bool(skip), threads=8)
+        full, ecl = O.full_pixel_search_batch(src.reshape(-1), refs.reshape(-1), stride, 16, 16,
+                                              jobs, "diamond", step_param, 1, skip=bool(skip),
+                                              cost_list=True, threads=8)
+        expected[skip] = (dia, full, ecl) + run(skip)
+    return M, run, expected
+
+
+@pytest.mark.parametrize("skip", [0, 1])
+@pytest.mark.parametrize("queued", [True, False])
+@pytest.mark.parametrize("cap", [8, 16])
+def test_capped_search_l1_cost(capped, cap, queued, skip):
+    """The capped 16x16 tiled DIAMOND search with a non-entropy mv cost: no
+    mvcost_dec_kernel runs, so the queue-fed launch's counters are zeroed by
+    lj_queue_zero.  Results and cost lists are the oracle's and, bit for bit,
+    the uncapped search's, twice in a row into poisoned buffers."""
+    M, run, expected = capped
+    dia, full, ecl, uncapped_out, uncapped_cl = expected[skip]
+    M.set_search_workgroup_cap(cap)
+    M.set_search_schedule(queued)
+    try:
+        for it in range(2):
+            got_out, got_cl = run(skip)
+            msg = "cap %d queued %s skip %d pass %d" % (cap, queued, skip, it)
+            res = got_out.view(M.RESULT_DTYPE)
+            for f in ("best_row", "best_col", "bestsme", "steps"):
+                np.testing.assert_array_equal(res[f], dia[f], err_msg=msg + " " + f)
+            for f in ("best_row", "best_col", "bestsme"):
+                np.testing.assert_array_equal(res[f], full[f], err_msg=msg + " " + f)
+            np.testing.assert_array_equal(got_cl, ecl, err_msg=msg + " cost list")
+            np.testing.assert_array_equal(got_out, uncapped_out, err_msg=msg + " vs uncapped")
+            np.testing.assert_array_equal(got_cl, uncapped_cl, err_msg=msg + " vs uncapped")
+    finally:
+        M.set_search_workgroup_cap(0)
+        M.set_search_schedule(True)
+
+
 def test_subpel_tree_upsampled_vs_reference(F):
     """lavish_find_best_sub_pixel_tree_batch_ex (SUBPEL_TREE, subpel_search_type
     USE_2_TAPS / USE_4_TAPS / USE_8_TAPS) against av1_find_best_sub_pixel_tree

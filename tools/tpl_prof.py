@@ -47,15 +47,12 @@ def main(reps=5):
     assert fn(buf, 1) == 0
     v = list(buf)
     steps = max(v[7], 1)
-    names = ["await", "after_wait_work", "before_wait_work", None, "publish"]
+    names = ["await", "ranking", "searches", None, "publish"]
     out = {"ms_per_call_host": round(ms, 4), "blocks": steps // reps,
            "cycles_per_step": {n: round(v[i] / steps, 1) for i, n in enumerate(names) if n},
-           "new_centre_after_wait_frac": round(v[3] / steps, 4),
            "walk_cycles_per_wave": round(v[5] / max(1, reps * tf.rows * tf.nrefs), 1),
-           "polls_ready_first_time": v[6],
-           "speculative_walk_cycles_per_step": {n: round(v[8 + i] / steps, 1) for i, n in enumerate(
-               ["centres", "window_fill", "ranking_sads", "sort_cut", "searches"])},
-           "searches_per_step": round(v[13] / steps, 3)}
+           "awaits_that_slept": v[6],
+           "steps_by_centres": {n: round(v[8 + n] / steps, 4) for n in (1, 2, 3, 4)}}
     print(json.dumps(out))
 
 
