@@ -37,6 +37,22 @@ const int16_t* dev_iscan(int tx_size, int tx_type);
 const int16_t* dev_iscan_rows(int tx_size);  // [3 kinds][KH][KW], lane-row order
 const int16_t* dev_scan(int tx_size, int tx_type);
 
+// LAVISH_QUANT_FP parameters the batch kernels take: the lowbd fast form of
+// quantize_fp (txq_dev.h) and the CHEAP form (rdo_kern.h) read quant as an
+// unsigned 16-bit factor and test "nonzero" on a non-negative product, and
+// the FAST block error holds |dqcoeff| <= |coeff| + dequant, which needs
+// quant * dequant near 2^16.  av1_build_quantizer's rows have quant_fp =
+// 2^16 / dequant > 0, so nothing real is refused.  (LAVISH_QUANT_B takes any
+// int16: invert_quant's quant is negative for most qindex.)
+constexpr int kErrQuantParams = -9;
+inline bool quant_fp_params_ok(const LavishQuantParams* p) {
+  for (int i = 0; i < 2; ++i)
+    if (p->quant[i] < 0 || p->dequant[i] <= 0 ||
+        (int32_t)p->quant[i] * p->dequant[i] > (1 << 17))
+      return false;
+  return true;
+}
+
 // lavish_txq_plane for the 64-point TX sizes (rdo.hip)
 int txq_plane_64(const int16_t* residual, int stride, int width, int height, int tx_size,
                  uint32_t type_mask, int bd, int quant_kind, const LavishQuantParams* qp,

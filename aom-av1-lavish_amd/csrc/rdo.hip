@@ -84,6 +84,7 @@ int rdo_plane(const uint16_t* src, const uint16_t* pred, int stride, int width, 
   if (tx_size < 0 || tx_size >= 19) return -1;
   if (qp == nullptr || out == nullptr || qcoeff == nullptr || dqcoeff == nullptr) return -3;
   if (bd != 8 && bd != 10 && bd != 12) return -3;
+  if (!quant_fp_params_ok(qp)) return kErrQuantParams;  // every decision mode runs quantize_fp
   const int W = tx_w(tx_size), H = tx_h(tx_size);
   if (width <= 0 || height <= 0 || stride < width) return -4;
   RdoArgs a{};
@@ -142,6 +143,8 @@ int rdo_frame(const uint16_t* src, const uint16_t* pred, int stride, int width, 
               uint32_t size_mask, const uint32_t* type_masks, int bd,
               const LavishQuantParams* qp, int rdmult, LavishRdoBlock* const* out,
               int32_t* const* qcoeff, int32_t* const* dqcoeff, hipStream_t caller, int px = 0) {
+  if (qp == nullptr) return -3;
+  if (!quant_fp_params_ok(qp)) return kErrQuantParams;
   int order[19], n = 0;
   for (int s = 0; s < 19; ++s)
     if ((size_mask >> s) & 1) order[n++] = s;

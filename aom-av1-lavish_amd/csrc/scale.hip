@@ -15,8 +15,9 @@
 // (the CONV_BUF stored) / average (plain or distance-weighted with the
 // buffer, then offset, round, clip).
 //
-// Blocks per 256-thread workgroup: NB = 256 / (w h) for blocks below 256
-// pixels (16 for 4x4, capped), one otherwise; each block's slice of the
+// Blocks per 256-thread workgroup: NB = the largest power of two <= 256 /
+// (w h) for blocks below 256 pixels (16 for 4x4, capped), one otherwise; each
+// block's slice of the
 // workgroup (256 / NB threads) runs the horizontal pass into the block's LDS
 // intermediate, a barrier, then the vertical pass.  The kernel is
 // instantiated per tap count pair (TX, TY) in {(8, 8), (12, 12), (4, 4),
@@ -249,7 +250,11 @@ int scale_batch(const void* src, int src_stride, void* dst, int dst_stride, uint
   // (rounded to 8 int16: each slot 16-byte aligned)
   const int im_rows = (((h - 1) * kMaxStep + (1 << kScaleBits) - 1) >> kScaleBits) + a.ty;
   a.im_cap = (im_rows * w + 7) & ~7;
-  a.nb = w * h >= 256 ? 1 : min(16, 256 / (w * h));
+  // a power of two, so that 256 / nb threads per slot leaves no thread over
+  // (h need not be a power of two: 8x3 would give 10 slots of 25 threads and
+  // six threads in an eleventh)
+  a.nb = 1;
+  while (a.nb < 16 && 2 * a.nb * w * h <= 256) a.nb *= 2;
   const int grid = (njobs + a.nb - 1) / a.nb;
   const size_t lds = (size_t)(2 * 16 * kFRow + a.nb * a.im_cap) * sizeof(int16_t);
   if (highbd)

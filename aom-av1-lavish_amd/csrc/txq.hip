@@ -66,9 +66,18 @@ __global__ __launch_bounds__(256) void quant_kernel(const int32_t* coeff, int n,
   int last = 0;
   for (int i = tid; i < n; i += 256) {
     const int rc = scan[i];
-    const int32_t q = quant_rt<LS>(coeff[base + rc], rc != 0, kind, highbd, qp);
+    const int32_t c = coeff[base + rc];
+    const int32_t q = quant_rt<LS>(c, rc != 0, kind, highbd, qp);
     qcoeff[base + rc] = q;
-    dqcoeff[base + rc] = dequant_one<LS>(q, rc != 0, qp);
+    // the reference dequantizes the quantized magnitude and puts the
+    // coefficient's sign back afterwards; the per-call quantizers take any
+    // int16 quant, and a negative one makes that magnitude negative, which
+    // >> log_scale rounds down (dequant_one takes |q|: the same bits for the
+    // tables' quant >= 0 only)
+    const int32_t cs = c >> 31, m = (q ^ cs) - cs;
+    const int32_t d = rc != 0 ? qp.dequant[1] : qp.dequant[0];
+    const int32_t dm = (int32_t)((uint32_t)m * (uint32_t)d) >> LS;
+    dqcoeff[base + rc] = (dm ^ cs) - cs;
     if (q != 0) last = max(last, i + 1);
   }
 #pragma unroll
@@ -178,6 +187,7 @@ int txq_plane(const int16_t* residual, int stride, int width, int height, int tx
   const int W = tx_w(tx_size), H = tx_h(tx_size);
   if (quant_kind < 0 || quant_kind > 2) return -3;
   if (quant_kind != LAVISH_QUANT_NONE && qp == nullptr) return -3;
+  if (quant_kind == LAVISH_QUANT_FP && !quant_fp_params_ok(qp)) return kErrQuantParams;
   if (width <= 0 || height <= 0 || stride < width) return -4;
   if (W > 32 || H > 32)  // 64-point sizes: rdo.hip, mode 0
     return txq_plane_64(residual, stride, width, height, tx_size, type_mask, bd, quant_kind, qp,
@@ -353,6 +363,8 @@ int txq_frame_plan(const int16_t* residual, int stride, int width, int height, u
                    const uint32_t* type_masks, int bd, int quant_kind, const LavishQuantParams* qp,
                    int32_t* const* qcoeff, int32_t* const* dqcoeff, uint16_t* const* eob, int cls,
                    TxqMulti& m, int& grid) {
+  if (quant_kind == LAVISH_QUANT_FP && qp != nullptr && !quant_fp_params_ok(qp))
+    return kErrQuantParams;
   int order[19], n = 0;
   for (int s = 0; s < 19; ++s)
     if (((size_mask >> s) & 1) && tx_w(s) <= 32 && tx_h(s) <= 32 && (txq_class(s) ? 1 : 0) == cls)
@@ -392,6 +404,8 @@ int txq_frame(const int16_t* residual, int stride, int width, int height, uint32
               const uint32_t* type_masks, int bd, int quant_kind, const LavishQuantParams* qp,
               int32_t* const* qcoeff, int32_t* const* dqcoeff, uint16_t* const* eob,
               hipStream_t caller) {
+  if (quant_kind == LAVISH_QUANT_FP && qp != nullptr && !quant_fp_params_ok(qp))
+    return kErrQuantParams;
   // 64-point sizes: their own path, first
   for (int s = 0; s < 19; ++s) {
     if (!((size_mask >> s) & 1) || (tx_w(s) <= 32 && tx_h(s) <= 32)) continue;

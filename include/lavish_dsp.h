@@ -65,7 +65,13 @@ typedef struct LavishTxfmParam {
 /* ------------------------------------------------------------------------ */
 /* The two-entry ([0]=DC, [1]=AC) tables a quantizer reads, i.e. one row of
  * the reference's QUANTS/Dequants (av1/encoder/av1_quantize.h).  For the fp
- * quantizer `round`/`quant` hold round_fp/quant_fp. */
+ * quantizer `round`/`quant` hold round_fp/quant_fp.
+ * The batch entry points (lavish_txq_plane / _frame / _frame_search with
+ * LAVISH_QUANT_FP, every lavish_rdo_plane* / lavish_rdo_frame* call) take fp
+ * rows with quant >= 0, dequant > 0 and quant * dequant <= 2^17 only, as
+ * av1_build_quantizer makes them (quant_fp = 2^16 / dequant), and return -9
+ * otherwise, nothing launched; LAVISH_QUANT_B rows and the per-call
+ * quantizer shims take any int16. */
 typedef struct LavishQuantParams {
   int16_t zbin[2];
   int16_t round[2];

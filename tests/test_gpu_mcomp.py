@@ -75,6 +75,58 @@ def test_diamond_edges_and_clamped_start(M, planes):
     _run(M, planes, 16, 16, start=(300, -300), ref_mv=(-40, 33))
 
 
+@pytest.fixture(scope="module")
+def tiled16(M, planes):
+    """The 16x16 DIAMOND search over tiled references (the form that reaches
+    launch_lj, csrc/mcomp_lj.hip) on the module's planes: device buffers, and
+    the oracle's results per (cost type, use_downsampled_sad), computed once."""
+    import torch
+    W, H, src, refs = planes
+    stride = src.shape[1]
+    jobs = M.frame_jobs(W, H, stride, BORDER, src.size, 16, 16, refs.shape[0], (13, -21), (2, -3))
+    # launch_lj's grid: eight jobs per wave, four waves per workgroup, rounded
+    # to 8 workgroups -- a cap of 8 must cut it
+    nwg = ((((len(jobs) + 7) // 8 + 3) // 4) + 7) & ~7
+    assert nwg > 8, nwg
+    ts, tr = torch.from_numpy(src).cuda(), torch.from_numpy(refs).cuda()
+    tiles = M.RefTiles(tr, ts.stride(0)).build()
+    dj = M.to_device(jobs)
+    out = torch.empty(len(jobs) * M.RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    expected = {}
+
+    def run(cost, skip):
+        out.fill_(0x55)
+        M.full_pixel_search_batch(ts, tr, 16, 16, dj, M.l1_cost_params(cost), "diamond", 1,
+                                  skip, out=out, tiles=tiles)
+        torch.cuda.synchronize()
+        if (cost, skip) not in expected:
+            expected[cost, skip] = O.diamond_batch(src.reshape(-1), refs.reshape(-1), stride, 16,
+                                                   16, jobs, 1, cost, skip, threads=8)
+        return M.results_numpy(out), expected[cost, skip]
+
+    return run
+
+
+@pytest.mark.parametrize("queued", [True, False])
+@pytest.mark.parametrize("cap", [8, 64, 0])
+@pytest.mark.parametrize("cost", [3, 4])  # MV_COST_L1_HDRES, MV_COST_NONE
+def test_capped_search_non_entropy_cost(M, tiled16, cost, cap, queued):
+    """A capped grid with a cost type that runs no mvcost_dec_kernel: the
+    queue counters are cleared by their own launch (lj_queue_zero).  Stale
+    counters would leave results unwritten, so each combination runs twice in
+    a row into poisoned outputs."""
+    M.set_search_workgroup_cap(cap)
+    M.set_search_schedule(queued)
+    try:
+        for it in range(2):
+            got, exp = tiled16(cost, True)
+            for f in ("best_row", "best_col", "bestsme", "steps"):
+                np.testing.assert_array_equal(got[f], exp[f], err_msg="pass %d %s" % (it, f))
+    finally:
+        M.set_search_workgroup_cap(0)
+        M.set_search_schedule(True)
+
+
 # ---- FAST_BIGDIA (pattern_search) ----
 
 @pytest.mark.parametrize("bw,bh", [(16, 16), (8, 8), (32, 32), (64, 64), (4, 4), (16, 8),

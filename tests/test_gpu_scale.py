@@ -166,6 +166,94 @@ def test_scale_batch_vs_oracle(S, bd, hb, w, h):
         np.testing.assert_array_equal(gd, ed, err_msg="mode %d dst" % mode)
 
 
+# heights that are not a power of two: the first six gave a slot count that
+# did not divide the workgroup (scale.hip, scale_batch), the next four always
+# had one block per workgroup, the last three are single rows
+ODD_SHAPES = [(8, 3), (4, 12), (4, 6), (16, 5), (2, 9), (2, 3),
+              (32, 9), (16, 24), (64, 3), (128, 5),
+              (2, 1), (16, 1), (128, 1)]
+
+
+@pytest.mark.parametrize("bd,hb", [(8, 0), (10, 1)])
+@pytest.mark.parametrize("w,h", ODD_SHAPES)
+def test_scale_batch_odd_heights_vs_oracle(S, bd, hb, w, h):
+    """37 blocks (more than a workgroup's slots, no multiple of them, three
+    workgroups or more) in buffers of a padded pitch with a gap row between
+    blocks; the whole poisoned buffer is compared, so a write outside a block
+    or into another workgroup's block shows."""
+    import torch
+    rng = np.random.default_rng(bd * 1000 + hb * 500 + w * 10 + h)
+    pdt = np.uint16 if hb else np.uint8
+    W, H = 2 * w + 48, 2 * h + 48
+    src = rng.integers(0, 1 << bd, (H, W)).astype(pdt)
+    nj = 37
+    jobs = _random_batch(S, rng, w, h, nj, W, H)
+    pitch, rows = w + 3, h + 1
+    jobs["dst_off"] = np.arange(nj) * rows * pitch + 1
+    jobs["conv_off"] = np.arange(nj) * rows * pitch + 2
+    fx, fy = O.interp_table(int(rng.integers(0, 5)), w), O.interp_table(int(rng.integers(0, 5)), h)
+    fpx, _ = _fp(fx)
+    fpy, _ = _fp(fy)
+    r0 = 3 + max(bd + 7 - 3 + 2 - 16, 0)
+    conv0 = rng.integers(0, 1 << (bd + 4), nj * rows * pitch).astype(np.uint16)
+    dst0 = rng.integers(0, 1 << bd, nj * rows * pitch).astype(pdt)
+    t = lambda a: torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a.copy()).cuda()
+    tjobs = torch.from_numpy(jobs.view(np.uint8)).cuda()
+    for mode in range(4):
+        comp = int(mode > 0)
+        cp = dict(do_average=int(mode > 1), round_0=r0,
+                  round_1=7 if comp else 2 * 7 - r0, is_compound=comp,
+                  use_dist_wtd_comp_avg=int(mode == 3), fwd_offset=9 if mode == 3 else 0,
+                  bck_offset=7 if mode == 3 else 0)
+        tsrc, tdst, tconv = t(src), t(dst0.copy()), t(conv0.copy())
+        S.convolve_2d_scale_batch(tsrc, W, tdst, pitch, tconv, pitch, w, h, tjobs, nj, fpx, fpy,
+                                  _cparams(cp), bd)
+        torch.cuda.synchronize()
+        gd = tdst.cpu().numpy().view(pdt)
+        gc = tconv.cpu().numpy().view(np.uint16)
+        ed, ec = dst0.copy(), conv0.copy()
+        for i in range(nj):
+            O.convolve_2d_scale(src, W, ed[int(jobs["dst_off"][i]):], pitch, w, h, fx, fy,
+                                *(int(jobs[f][i]) for f in FIELDS), cp,
+                                ec[int(jobs["conv_off"][i]):], pitch, bd, hb,
+                                src_off=int(jobs["src_off"][i]))
+        np.testing.assert_array_equal(gc, ec, err_msg="mode %d conv" % mode)
+        np.testing.assert_array_equal(gd, ed, err_msg="mode %d dst" % mode)
+        if mode == 0:  # the oracle did write the blocks and nothing else
+            assert (ed != dst0).any() and (ec == conv0).all()
+            m = np.zeros((nj, rows, pitch), bool)
+            m[:, :h, 1:1 + w] = True
+            assert (ed == dst0)[~m.reshape(-1)].all()
+
+
+@pytest.mark.parametrize("w,h", [(8, 3), (16, 5)])
+def test_scale_shims_odd_heights_vs_oracle(S, w, h):
+    rng = np.random.default_rng(w * 100 + h)
+    fx, fy = O.interp_table(0, w), O.interp_table(0, h)
+    fpx, _ = _fp(fx)
+    fpy, _ = _fp(fy)
+    for bd, pdt in ((8, np.uint8), (10, np.uint16)):
+        hb = int(pdt == np.uint16)
+        W, H = 2 * w + 48, 2 * h + 48
+        src = rng.integers(0, 1 << bd, (H, W)).astype(pdt)
+        org = 10 * W + 10
+        r0 = 3 + max(bd + 7 - 3 + 2 - 16, 0)
+        cp = dict(do_average=0, round_0=r0, round_1=14 - r0, is_compound=0,
+                  use_dist_wtd_comp_avg=0, fwd_offset=0, bck_offset=0)
+        for spx, xs, spy, ys in ((0, 1024, 0, 1024), (517, 1536, 1023, 2048), (64, 700, 900, 1)):
+            ds = w + 5
+            dst0 = rng.integers(0, 1 << bd, (h + 2, ds)).astype(pdt)
+            got, exp = dst0.copy(), dst0.copy()
+            conv = np.zeros((h, w), np.uint16)
+            S.convolve_2d_scale_shim(ctypes.c_void_p(src.ctypes.data + org * src.itemsize), W,
+                                     got, ds, w, h, fpx, fpy, spx, xs, spy, ys,
+                                     _cparams(cp, conv, w), bd)
+            O.convolve_2d_scale(src, W, exp, ds, w, h, fx, fy, spx, xs, spy, ys, cp,
+                                np.zeros((h, w), np.uint16), w, bd, hb, src_off=org)
+            np.testing.assert_array_equal(got, exp, err_msg=str((bd, spx, xs, spy, ys)))
+            assert (exp[:h, :w] != dst0[:h, :w]).any()
+
+
 def test_scale_out_of_range_steps_untouched(S):
     """Steps outside [1, 2048] or phases outside [0, 1023]: the block's
     outputs are left as they were; the in-range blocks of the same batch are
