@@ -19,19 +19,9 @@
 //   sum_sse_2d_i16          aom_dsp/sum_squares.c:75-90
 //   get_blk_sse_sum         aom_dsp/blk_sse_sum.c:14-27
 #include "lavish_internal.h"
+#include "pixel_dev.h"
 
 namespace lavish {
-
-__device__ __forceinline__ int64_t wave_sum64(int64_t v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t v) {
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
 
 // ---------------------------------------------------------------- SAD ----
 // mode 0: SAD, 1: 2 x SAD of even rows (sad_skip), 2: SAD against the
@@ -71,33 +61,6 @@ __global__ __launch_bounds__(64) void sad_kernel(const Pix* src, int ss, const P
 //        second_pred, ROUND_POWER_OF_TWO(a + b, 1) per byte);
 //   variance: sum = sad(a, 0) - sad(b, 0), sse = a.a + b.b - 2 a.b with
 //        v_dot4_u32_u8 (exact mod 2^32; the true sse < 2^32 for 8-bit).
-struct U8Shape {
-  int lw4;   // log2(w / 4)
-  int lc;    // log2(words per chunk)
-  int lcpr;  // log2(chunks per row)
-  int lpj;   // lanes per job (power of two, <= 64)
-  int chunks;
-};
-
-__device__ __forceinline__ void load_words(const uint8_t* p, int c, uint32_t (&w)[4]) {
-  if (c == 4) {
-    const u32x4u v = *(const __attribute__((address_space(1))) u32x4u*)p;
-    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-  } else if (c == 2) {
-    const u32x2u v = *(const __attribute__((address_space(1))) u32x2u*)p;
-    w[0] = v.x; w[1] = v.y; w[2] = 0; w[3] = 0;
-  } else {
-    w[0] = *(const __attribute__((address_space(1))) u32u*)p;
-    w[1] = 0; w[2] = 0; w[3] = 0;
-  }
-}
-
-// sum over the LPJ-lane group of a job (every lane of the group gets it)
-__device__ __forceinline__ uint32_t group_sum(uint32_t v, int lpj) {
-  for (int m = 1; m < lpj; m <<= 1) v += __shfl_xor(v, m);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void sad_u8_kernel(const uint8_t* __restrict__ src, int ss,
                                                      const uint8_t* __restrict__ ref, int rs,
                                                      U8Shape sh, const LavishPixJob* __restrict__ jobs,
@@ -179,10 +142,6 @@ __global__ __launch_bounds__(256) void var_u8_kernel(const uint8_t* __restrict__
 // chunks of up to 8 samples = one 16-byte load): SAD on v_sad_u16; variance
 // with exact 64-bit per-lane sums, then highbd_variance64's rounding for
 // 10 / 12 bits (aom_dsp/variance.c:321-408) as var_kernel does it.
-__device__ __forceinline__ void load_words16(const uint16_t* p, int c, uint32_t (&w)[4]) {
-  load_words((const uint8_t*)p, c, w);
-}
-
 __global__ __launch_bounds__(256) void sad_u16_kernel(const uint16_t* __restrict__ src, int ss,
                                                       const uint16_t* __restrict__ ref, int rs,
                                                       U8Shape sh, const LavishPixJob* __restrict__ jobs,
@@ -286,31 +245,6 @@ __global__ __launch_bounds__(256) void var_u16_kernel(const uint16_t* __restrict
       var_out[j] = v >= 0 ? (uint32_t)v : 0;
     }
   }
-}
-
-static int ilog2(int v) { return 31 - __builtin_clz(v); }
-
-// the u16 word-chunk layout (2 samples per word, chunks of <= 8 samples)
-static bool u16_shape(int w, int rows, U8Shape& sh) {
-  if (w < 2 || (w & (w - 1)) || rows < 1 || (rows & (rows - 1))) return false;
-  sh.lw4 = ilog2(w / 2);  // log2(words per row)
-  sh.lc = sh.lw4 < 2 ? sh.lw4 : 2;
-  sh.lcpr = sh.lw4 - sh.lc;
-  sh.chunks = rows << sh.lcpr;
-  sh.lpj = sh.chunks < 64 ? sh.chunks : 64;
-  return true;
-}
-
-// the u8 word-chunk layout of a w x h block with `rows` rows read; false when
-// w or rows is not a power of two >= 4 / >= 1
-static bool u8_shape(int w, int rows, U8Shape& sh) {
-  if (w < 4 || (w & (w - 1)) || rows < 1 || (rows & (rows - 1))) return false;
-  sh.lw4 = ilog2(w / 4);
-  sh.lc = sh.lw4 < 2 ? sh.lw4 : 2;
-  sh.lcpr = sh.lw4 - sh.lc;
-  sh.chunks = rows << sh.lcpr;
-  sh.lpj = sh.chunks < 64 ? sh.chunks : 64;
-  return true;
 }
 
 // ------------------------------------------------------------ variance ----

@@ -1,6 +1,7 @@
 // pixel_shims.hip -- per-call RTCD shims (host pointers) for the pixel-domain
 // kernels of pixel.hip: SAD, variance, MSE, SSE, subtract, sum of squares,
-// Hadamard, SATD, block error.  Each call stages the caller's block(s) into a
+// Hadamard, SATD, block error, and for the masked / OBMC / distance-weighted
+// kernels of pixel_comp.hip.  Each call stages the caller's block(s) into a
 // per-thread device scratch (hipMemcpy2DAsync, so only the w x h window of a
 // strided plane is read), runs the batch kernel on a single job, and copies
 // the result back.  Drop-in parity, not speed (SURVEY.md 8(b) "Granularity").
@@ -113,6 +114,123 @@ uint32_t var_shim(const uint8_t* a8, int as, const uint8_t* b8, int bs, int w, i
   if (sum) st.copy_out(sum, dsum, 1);
   st.sync();
   return v;
+}
+
+// masked (mode 0) / distance-weighted (mode 1) SAD against nrefs references
+template <typename Pix>
+void comp_sad_shim(const uint8_t* src8, int ss, const uint8_t* const* refs8, int nrefs, int rs,
+                   int w, int h, int mode, const uint8_t* second8, const uint8_t* msk, int ms,
+                   int invert, const LavishDistWtdCompParams* jcp, unsigned* out) {
+  Stage st(kStageCap);
+  const Pix* src = st.block(untag<Pix>(src8), ss, w, h);
+  Pix* ref = (Pix*)st.take((size_t)nrefs * w * h * sizeof(Pix));
+  LavishCompJob jb{};
+  for (int k = 0; k < nrefs; ++k) {
+    LAVISH_CHECK(hipMemcpy2DAsync(ref + (size_t)k * w * h, (size_t)w * sizeof(Pix),
+                                  untag<Pix>(refs8[k]), (size_t)rs * sizeof(Pix),
+                                  (size_t)w * sizeof(Pix), h, hipMemcpyHostToDevice, st.s));
+    jb.ref_off[k] = (int64_t)k * w * h;
+  }
+  const Pix* second = st.copy_in(untag<Pix>(second8), (size_t)w * h);
+  const uint8_t* dmsk = mode == 0 ? st.block(msk, ms, w, h) : nullptr;
+  jb.invert_mask = invert;
+  const LavishCompJob* djob = st.copy_in(&jb, 1);
+  uint32_t* dout = (uint32_t*)st.take(4 * sizeof(uint32_t));
+  must(lavish_comp_sad_batch(src, w, ref, w, w, h, djob, 1, nrefs, mode, second, dmsk, w,
+                             jcp ? jcp->fwd_offset : 0, jcp ? jcp->bck_offset : 0,
+                             sizeof(Pix) == 2, dout, st.s),
+       "lavish_comp_sad_batch");
+  uint32_t r[4] = {0, 0, 0, 0};
+  st.copy_out(r, dout, nrefs);
+  st.sync();
+  for (int k = 0; k < nrefs; ++k) out[k] = r[k];
+}
+
+template <typename Pix>
+unsigned comp_sad1(const uint8_t* src, int ss, const uint8_t* ref, int rs, int w, int h, int mode,
+                   const uint8_t* second, const uint8_t* msk, int ms, int invert,
+                   const LavishDistWtdCompParams* jcp) {
+  unsigned r = 0;
+  const uint8_t* refs[1] = {ref};
+  comp_sad_shim<Pix>(src, ss, refs, 1, rs, w, h, mode, second, msk, ms, invert, jcp, &r);
+  return r;
+}
+
+// masked (kind 0) / distance-weighted (kind 1) sub-pixel variance
+template <typename Pix>
+uint32_t comp_var_shim(const uint8_t* a8, int as, int xoff, int yoff, const uint8_t* b8, int bs,
+                       int w, int h, int kind, int bd, const uint8_t* second8, const uint8_t* msk,
+                       int ms, int invert, const LavishDistWtdCompParams* jcp, uint32_t* sse) {
+  Stage st(kStageCap);
+  const Pix* a = st.block(untag<Pix>(a8), as, w + 1, h + 1);
+  const Pix* b = st.block(untag<Pix>(b8), bs, w, h);
+  const Pix* second = st.copy_in(untag<Pix>(second8), (size_t)w * h);
+  const uint8_t* dmsk = kind == 0 ? st.block(msk, ms, w, h) : nullptr;
+  LavishCompJob jb{};
+  jb.xoff = xoff;
+  jb.yoff = yoff;
+  jb.invert_mask = invert;
+  const LavishCompJob* djob = st.copy_in(&jb, 1);
+  uint32_t* dv = (uint32_t*)st.take(64);
+  uint32_t* ds = (uint32_t*)st.take(64);
+  must(lavish_comp_variance_batch(a, w + 1, b, w, w, h, djob, 1, kind, bd, sizeof(Pix) == 2,
+                                  second, dmsk, w, jcp ? jcp->fwd_offset : 0,
+                                  jcp ? jcp->bck_offset : 0, dv, ds, st.s),
+       "lavish_comp_variance_batch");
+  uint32_t v = 0;
+  st.copy_out(&v, dv, 1);
+  if (sse) st.copy_out(sse, ds, 1);
+  st.sync();
+  return v;
+}
+
+// OBMC SAD (kind 0) / variance (1) / sub-pixel variance (2); wsrc and mask
+// are contiguous w x h int32 blocks
+template <typename Pix>
+unsigned obmc_shim(const uint8_t* pre8, int ps, int w, int h, int kind, int bd, int xoff, int yoff,
+                   const int32_t* wsrc, const int32_t* mask, unsigned* sse) {
+  Stage st(kStageCap);
+  const int sub = kind == 2;
+  const Pix* pre = st.block(untag<Pix>(pre8), ps, w + sub, h + sub);
+  const int32_t* dw = st.copy_in(wsrc, (size_t)w * h);
+  const int32_t* dm = st.copy_in(mask, (size_t)w * h);
+  LavishCompJob jb{};
+  jb.xoff = xoff;
+  jb.yoff = yoff;
+  const LavishCompJob* djob = st.copy_in(&jb, 1);
+  uint32_t* dv = (uint32_t*)st.take(64);
+  uint32_t* ds = (uint32_t*)st.take(64);
+  must(lavish_obmc_batch(pre, w + sub, w, h, djob, 1, 1, kind, bd, sizeof(Pix) == 2, dw, dm, dv,
+                         ds, st.s),
+       "lavish_obmc_batch");
+  uint32_t v = 0, s = 0;
+  st.copy_out(&v, dv, 1);
+  if (sse) st.copy_out(&s, ds, 1);
+  st.sync();
+  if (sse) *sse = s;
+  return v;
+}
+
+// aom_comp_avg_pred (mode 0) / aom_dist_wtd_comp_avg_pred (1) /
+// aom_comp_mask_pred (2): comp_pred and pred are contiguous w x h
+template <typename Pix>
+void comp_pred_shim(uint8_t* comp8, const uint8_t* pred8, int w, int h, const uint8_t* ref8, int rs,
+                    int mode, const uint8_t* msk, int ms, int invert,
+                    const LavishDistWtdCompParams* jcp) {
+  Stage st(kStageCap);
+  const Pix* pred = st.copy_in(untag<Pix>(pred8), (size_t)w * h);
+  const Pix* ref = st.block(untag<Pix>(ref8), rs, w, h);
+  const uint8_t* dmsk = mode == 2 ? st.block(msk, ms, w, h) : nullptr;
+  Pix* dcomp = (Pix*)st.take((size_t)w * h * sizeof(Pix));
+  LavishCompJob jb{};
+  jb.invert_mask = invert;
+  const LavishCompJob* djob = st.copy_in(&jb, 1);
+  must(lavish_comp_pred_batch(dcomp, pred, w, h, ref, w, djob, 1, mode, dmsk, w,
+                              jcp ? jcp->fwd_offset : 0, jcp ? jcp->bck_offset : 0,
+                              sizeof(Pix) == 2, st.s),
+       "lavish_comp_pred_batch");
+  st.copy_out(untag<Pix>(comp8), dcomp, (size_t)w * h);
+  st.sync();
 }
 
 template <typename Pix>
@@ -339,6 +457,101 @@ extern "C" {
 
 LAVISH_ENCODER_BLOCK_SIZES(SAD_SHIMS)
 LAVISH_ENCODER_BLOCK_SIZES(VAR_SHIMS)
+
+// ---- masked / OBMC / distance-weighted (pixel_comp.hip) ----
+#define COMP_SAD_SHIMS(w, h)                                                                      \
+  unsigned int aom_masked_sad##w##x##h##_hip(const uint8_t* s, int ss, const uint8_t* r, int rs,  \
+                                             const uint8_t* sp, const uint8_t* m, int ms,         \
+                                             int inv) {                                           \
+    return comp_sad1<uint8_t>(s, ss, r, rs, w, h, 0, sp, m, ms, inv, nullptr);                    \
+  }                                                                                               \
+  void aom_masked_sad##w##x##h##x4d_hip(const uint8_t* s, int ss, const uint8_t* r[4], int rs,    \
+                                        const uint8_t* sp, const uint8_t* m, int ms, int inv,     \
+                                        unsigned sads[4]) {                                       \
+    comp_sad_shim<uint8_t>(s, ss, r, 4, rs, w, h, 0, sp, m, ms, inv, nullptr, sads);              \
+  }                                                                                               \
+  unsigned int aom_highbd_masked_sad##w##x##h##_hip(const uint8_t* s, int ss, const uint8_t* r,   \
+                                                    int rs, const uint8_t* sp, const uint8_t* m,  \
+                                                    int ms, int inv) {                            \
+    return comp_sad1<uint16_t>(s, ss, r, rs, w, h, 0, sp, m, ms, inv, nullptr);                   \
+  }                                                                                               \
+  unsigned int aom_obmc_sad##w##x##h##_hip(const uint8_t* p, int ps, const int32_t* ws,           \
+                                           const int32_t* m) {                                    \
+    return obmc_shim<uint8_t>(p, ps, w, h, 0, 8, 0, 0, ws, m, nullptr);                           \
+  }                                                                                               \
+  unsigned int aom_highbd_obmc_sad##w##x##h##_hip(const uint8_t* p, int ps, const int32_t* ws,    \
+                                                  const int32_t* m) {                             \
+    return obmc_shim<uint16_t>(p, ps, w, h, 0, 8, 0, 0, ws, m, nullptr);                          \
+  }                                                                                               \
+  unsigned int aom_dist_wtd_sad##w##x##h##_avg_hip(const uint8_t* s, int ss, const uint8_t* r,    \
+                                                   int rs, const uint8_t* sp,                     \
+                                                   const LavishDistWtdCompParams* jcp) {          \
+    return comp_sad1<uint8_t>(s, ss, r, rs, w, h, 1, sp, nullptr, 0, 0, jcp);                     \
+  }                                                                                               \
+  unsigned int aom_highbd_dist_wtd_sad##w##x##h##_avg_hip(                                        \
+      const uint8_t* s, int ss, const uint8_t* r, int rs, const uint8_t* sp,                      \
+      const LavishDistWtdCompParams* jcp) {                                                       \
+    return comp_sad1<uint16_t>(s, ss, r, rs, w, h, 1, sp, nullptr, 0, 0, jcp);                    \
+  }
+
+#define COMP_VAR_SHIMS_BD(pre, Pix, bd, w, h)                                                     \
+  unsigned int pre##masked_sub_pixel_variance##w##x##h##_hip(                                     \
+      const uint8_t* s, int ss, int xo, int yo, const uint8_t* r, int rs, const uint8_t* sp,      \
+      const uint8_t* m, int ms, int inv, unsigned int* sse) {                                     \
+    return comp_var_shim<Pix>(s, ss, xo, yo, r, rs, w, h, 0, bd, sp, m, ms, inv, nullptr, sse);   \
+  }                                                                                               \
+  uint32_t pre##dist_wtd_sub_pixel_avg_variance##w##x##h##_hip(                                   \
+      const uint8_t* s, int ss, int xo, int yo, const uint8_t* r, int rs, uint32_t* sse,          \
+      const uint8_t* sp, const LavishDistWtdCompParams* jcp) {                                    \
+    return comp_var_shim<Pix>(s, ss, xo, yo, r, rs, w, h, 1, bd, sp, nullptr, 0, 0, jcp, sse);    \
+  }
+#define OBMC_VAR_SHIMS_BD(pre, Pix, bd, w, h)                                                     \
+  unsigned int pre##obmc_variance##w##x##h##_hip(const uint8_t* p, int ps, const int32_t* ws,     \
+                                                 const int32_t* m, unsigned int* sse) {           \
+    return obmc_shim<Pix>(p, ps, w, h, 1, bd, 0, 0, ws, m, sse);                                  \
+  }                                                                                               \
+  unsigned int pre##obmc_sub_pixel_variance##w##x##h##_hip(const uint8_t* p, int ps, int xo,      \
+                                                           int yo, const int32_t* ws,             \
+                                                           const int32_t* m, unsigned int* sse) { \
+    return obmc_shim<Pix>(p, ps, w, h, 2, bd, xo, yo, ws, m, sse);                                \
+  }
+#define COMP_VAR_SHIMS(w, h)                              \
+  COMP_VAR_SHIMS_BD(aom_, uint8_t, 8, w, h)               \
+  COMP_VAR_SHIMS_BD(aom_highbd_8_, uint16_t, 8, w, h)     \
+  COMP_VAR_SHIMS_BD(aom_highbd_10_, uint16_t, 10, w, h)   \
+  COMP_VAR_SHIMS_BD(aom_highbd_12_, uint16_t, 12, w, h)   \
+  OBMC_VAR_SHIMS_BD(aom_, uint8_t, 8, w, h)               \
+  OBMC_VAR_SHIMS_BD(aom_highbd_, uint16_t, 8, w, h)       \
+  OBMC_VAR_SHIMS_BD(aom_highbd_10_, uint16_t, 10, w, h)   \
+  OBMC_VAR_SHIMS_BD(aom_highbd_12_, uint16_t, 12, w, h)
+
+LAVISH_ENCODER_BLOCK_SIZES(COMP_SAD_SHIMS)
+LAVISH_ENCODER_BLOCK_SIZES(COMP_VAR_SHIMS)
+
+void aom_comp_avg_pred_hip(uint8_t* cp, const uint8_t* p, int w, int h, const uint8_t* r, int rs) {
+  comp_pred_shim<uint8_t>(cp, p, w, h, r, rs, 0, nullptr, 0, 0, nullptr);
+}
+void aom_dist_wtd_comp_avg_pred_hip(uint8_t* cp, const uint8_t* p, int w, int h, const uint8_t* r,
+                                    int rs, const LavishDistWtdCompParams* jcp) {
+  comp_pred_shim<uint8_t>(cp, p, w, h, r, rs, 1, nullptr, 0, 0, jcp);
+}
+void aom_comp_mask_pred_hip(uint8_t* cp, const uint8_t* p, int w, int h, const uint8_t* r, int rs,
+                            const uint8_t* m, int ms, int inv) {
+  comp_pred_shim<uint8_t>(cp, p, w, h, r, rs, 2, m, ms, inv, nullptr);
+}
+void aom_highbd_comp_avg_pred_hip(uint8_t* cp, const uint8_t* p, int w, int h, const uint8_t* r,
+                                  int rs) {
+  comp_pred_shim<uint16_t>(cp, p, w, h, r, rs, 0, nullptr, 0, 0, nullptr);
+}
+void aom_highbd_dist_wtd_comp_avg_pred_hip(uint8_t* cp, const uint8_t* p, int w, int h,
+                                           const uint8_t* r, int rs,
+                                           const LavishDistWtdCompParams* jcp) {
+  comp_pred_shim<uint16_t>(cp, p, w, h, r, rs, 1, nullptr, 0, 0, jcp);
+}
+void aom_highbd_comp_mask_pred_hip(uint8_t* cp, const uint8_t* p, int w, int h, const uint8_t* r,
+                                   int rs, const uint8_t* m, int ms, int inv) {
+  comp_pred_shim<uint16_t>(cp, p, w, h, r, rs, 2, m, ms, inv, nullptr);
+}
 
 #define MSE_SHIMS(pre, Pix, bd)                                                                 \
   void pre##get16x16var_hip(const uint8_t* s, int ss, const uint8_t* r, int rs,                 \

@@ -8,6 +8,10 @@ subtract, sum of squares, Hadamard, SATD, block error.
   before the call, so the shims see what the reference's callers pass.
 * Batch layer: ``sad_batch``, ``variance_batch`` ... on torch device tensors
   with a LavishPixJob table (include/lavish_dsp.h).
+* Masked / OBMC / distance-weighted forms (csrc/pixel_comp.hip): per-call
+  ``masked_sad``, ``obmc_variance``, ``dist_wtd_sad_avg``, ``comp_pred`` ...;
+  batch ``comp_sad_batch``, ``comp_variance_batch``, ``obmc_batch``,
+  ``comp_pred_batch`` with a LavishCompJob table (``comp_jobs_tensor``).
 """
 import ctypes
 
@@ -105,6 +109,34 @@ _proto("av1_highbd_iwht4x4_16_add", None, [_vp, _vp, _i32, _i32])
 _proto("av1_highbd_iwht4x4_1_add", None, [_vp, _vp, _i32, _i32])
 _proto("av1_block_error", ctypes.c_int64, [_vp, _vp, _ssz, _vp])
 _proto("av1_highbd_block_error", ctypes.c_int64, [_vp, _vp, _ssz, _vp, _i32])
+
+
+# masked / OBMC / distance-weighted (csrc/pixel_comp.hip)
+_MSAD = [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32]
+_OSAD = [_vp, _i32, _vp, _vp]
+_JSAD = [_vp, _i32, _vp, _i32, _vp, _vp]
+_MSVAR = [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _vp]
+_JSVAR = [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp]
+for _w, _h in ENCODER_BLOCK_SIZES:
+    _s = "%dx%d" % (_w, _h)
+    _proto("aom_masked_sad" + _s, ctypes.c_uint, _MSAD)
+    _proto("aom_masked_sad%sx4d" % _s, None, _MSAD + [_vp])
+    _proto("aom_highbd_masked_sad" + _s, ctypes.c_uint, _MSAD)
+    _proto("aom_obmc_sad" + _s, ctypes.c_uint, _OSAD)
+    _proto("aom_highbd_obmc_sad" + _s, ctypes.c_uint, _OSAD)
+    _proto("aom_dist_wtd_sad%s_avg" % _s, ctypes.c_uint, _JSAD)
+    _proto("aom_highbd_dist_wtd_sad%s_avg" % _s, ctypes.c_uint, _JSAD)
+    for _pre in ("aom_", "aom_highbd_8_", "aom_highbd_10_", "aom_highbd_12_"):
+        _proto(_pre + "masked_sub_pixel_variance" + _s, ctypes.c_uint, _MSVAR)
+        _proto(_pre + "dist_wtd_sub_pixel_avg_variance" + _s, ctypes.c_uint32, _JSVAR)
+    for _pre in ("aom_", "aom_highbd_", "aom_highbd_10_", "aom_highbd_12_"):
+        _proto(_pre + "obmc_variance" + _s, ctypes.c_uint, _OSAD + [_vp])
+        _proto(_pre + "obmc_sub_pixel_variance" + _s, ctypes.c_uint,
+               [_vp, _i32, _i32, _i32, _vp, _vp, _vp])
+for _pre in ("aom_", "aom_highbd_"):
+    _proto(_pre + "comp_avg_pred", None, [_vp, _vp, _i32, _i32, _vp, _i32])
+    _proto(_pre + "dist_wtd_comp_avg_pred", None, [_vp, _vp, _i32, _i32, _vp, _i32, _vp])
+    _proto(_pre + "comp_mask_pred", None, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32])
 
 
 def rtcd(name):
@@ -266,7 +298,111 @@ def block_error(coeff, dqcoeff, n, bd=None):
     return e, int(ssz[0])
 
 
+# ---------------------------- masked / OBMC / distance-weighted per-call --
+class DistWtdCompParams(ctypes.Structure):
+    """DIST_WTD_COMP_PARAMS (av1/common/blockd.h:554-558)."""
+    _fields_ = [("use_dist_wtd_comp_avg", ctypes.c_int), ("fwd_offset", ctypes.c_int),
+                ("bck_offset", ctypes.c_int)]
+
+
+def _jcp(fwd_offset, bck_offset):
+    return ctypes.byref(DistWtdCompParams(1, fwd_offset, bck_offset))
+
+
+def _opre(bd, highbd):
+    """Prefix of the OBMC variance names: aom_highbd_ for 8 bits, not _8_."""
+    if not highbd:
+        return "aom_"
+    return "aom_highbd_" if bd == 8 else "aom_highbd_%d_" % bd
+
+
+def masked_sad(w, h, src, src_stride, ref, ref_stride, second_pred, mask, mask_stride,
+               invert_mask, highbd=False):
+    pre = "aom_highbd_" if highbd else "aom_"
+    return _PROTOS["%smasked_sad%dx%d" % (pre, w, h)](
+        _ptr(src, highbd), src_stride, _ptr(ref, highbd), ref_stride, _ptr(second_pred, highbd),
+        _ptr(mask), mask_stride, invert_mask)
+
+
+def masked_sad_x4d(w, h, src, src_stride, refs, ref_stride, second_pred, mask, mask_stride,
+                   invert_mask):
+    """aom_masked_sad{w}x{h}x4d (lowbd only).  Returns uint32[4]."""
+    out = np.zeros(4, np.uint32)
+    arr = (_vp * 4)(*[_ptr(r).value for r in refs])
+    _PROTOS["aom_masked_sad%dx%dx4d" % (w, h)](
+        _ptr(src), src_stride, ctypes.cast(arr, _vp), ref_stride, _ptr(second_pred), _ptr(mask),
+        mask_stride, invert_mask, _ptr(out))
+    return out
+
+
+def masked_sub_pixel_variance(w, h, src, src_stride, xoff, yoff, ref, ref_stride, second_pred,
+                              mask, mask_stride, invert_mask, bd=8, highbd=False):
+    """(var, sse); `src` is the filtered operand, as in the reference."""
+    sse = np.zeros(1, np.uint32)
+    v = _PROTOS["%smasked_sub_pixel_variance%dx%d" % (_vpre(bd, highbd), w, h)](
+        _ptr(src, highbd), src_stride, xoff, yoff, _ptr(ref, highbd), ref_stride,
+        _ptr(second_pred, highbd), _ptr(mask), mask_stride, invert_mask, _ptr(sse))
+    return v, int(sse[0])
+
+
+def obmc_sad(w, h, pre, pre_stride, wsrc, mask, highbd=False):
+    name = ("aom_highbd_obmc_sad%dx%d" if highbd else "aom_obmc_sad%dx%d") % (w, h)
+    return _PROTOS[name](_ptr(pre, highbd), pre_stride, _ptr(wsrc), _ptr(mask))
+
+
+def obmc_variance(w, h, pre, pre_stride, wsrc, mask, bd=8, highbd=False):
+    sse = np.zeros(1, np.uint32)
+    v = _PROTOS["%sobmc_variance%dx%d" % (_opre(bd, highbd), w, h)](
+        _ptr(pre, highbd), pre_stride, _ptr(wsrc), _ptr(mask), _ptr(sse))
+    return v, int(sse[0])
+
+
+def obmc_sub_pixel_variance(w, h, pre, pre_stride, xoff, yoff, wsrc, mask, bd=8, highbd=False):
+    sse = np.zeros(1, np.uint32)
+    v = _PROTOS["%sobmc_sub_pixel_variance%dx%d" % (_opre(bd, highbd), w, h)](
+        _ptr(pre, highbd), pre_stride, xoff, yoff, _ptr(wsrc), _ptr(mask), _ptr(sse))
+    return v, int(sse[0])
+
+
+def dist_wtd_sad_avg(w, h, src, src_stride, ref, ref_stride, second_pred, fwd_offset, bck_offset,
+                     highbd=False):
+    pre = "aom_highbd_" if highbd else "aom_"
+    return _PROTOS["%sdist_wtd_sad%dx%d_avg" % (pre, w, h)](
+        _ptr(src, highbd), src_stride, _ptr(ref, highbd), ref_stride, _ptr(second_pred, highbd),
+        _jcp(fwd_offset, bck_offset))
+
+
+def dist_wtd_sub_pixel_avg_variance(w, h, src, src_stride, xoff, yoff, ref, ref_stride,
+                                    second_pred, fwd_offset, bck_offset, bd=8, highbd=False):
+    sse = np.zeros(1, np.uint32)
+    v = _PROTOS["%sdist_wtd_sub_pixel_avg_variance%dx%d" % (_vpre(bd, highbd), w, h)](
+        _ptr(src, highbd), src_stride, xoff, yoff, _ptr(ref, highbd), ref_stride, _ptr(sse),
+        _ptr(second_pred, highbd), _jcp(fwd_offset, bck_offset))
+    return v, int(sse[0])
+
+
+def comp_pred(comp_pred, pred, w, h, ref, ref_stride, mode="avg", mask=None, mask_stride=0,
+              invert_mask=0, fwd_offset=0, bck_offset=0, highbd=False):
+    """aom[_highbd]_comp_avg_pred ("avg"), _dist_wtd_comp_avg_pred ("dist_wtd")
+    or _comp_mask_pred ("mask") into the contiguous w x h `comp_pred`."""
+    pre = "aom_highbd_" if highbd else "aom_"
+    a = [_ptr(comp_pred, highbd), _ptr(pred, highbd), w, h, _ptr(ref, highbd), ref_stride]
+    if mode == "avg":
+        _PROTOS[pre + "comp_avg_pred"](*a)
+    elif mode == "dist_wtd":
+        _PROTOS[pre + "dist_wtd_comp_avg_pred"](*a, _jcp(fwd_offset, bck_offset))
+    elif mode == "mask":
+        _PROTOS[pre + "comp_mask_pred"](*a, _ptr(mask), mask_stride, invert_mask)
+    else:
+        raise ValueError("comp_pred mode %r" % (mode,))
+
+
 # ------------------------------------------------------------ batch layer --
+COMP_JOB_DTYPE = np.dtype([("src_off", "<i8"), ("ref_off", "<i8", (4,)), ("second_off", "<i8"),
+                           ("mask_off", "<i8"), ("xoff", "<i4"), ("yoff", "<i4"),
+                           ("invert_mask", "<i4"), ("reserved", "<i4")], align=True)
+assert COMP_JOB_DTYPE.itemsize == 72
+
 for _n, _a in (
         ("lavish_sad_batch", [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _i32,
                               _vp, _vp]),
@@ -282,6 +418,14 @@ for _n, _a in (
         ("lavish_satd_lp_batch", [_vp, _i32, _i32, _vp, _vp]),
         ("lavish_block_error_lp_batch", [_vp, _vp, _i32, _i32, _vp, _vp]),
         ("lavish_sum_sse_batch", [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp]),
+        ("lavish_comp_sad_batch", [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp,
+                                   _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+        ("lavish_comp_variance_batch", [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32,
+                                        _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
+        ("lavish_obmc_batch", [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp,
+                               _vp, _vp, _vp]),
+        ("lavish_comp_pred_batch", [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _i32,
+                                    _i32, _i32, _i32, _vp]),
         ("lavish_fwht4x4_batch", [_vp, _i32, _vp, _i32, _vp, _vp]),
         ("lavish_iwht4x4_add_batch", [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp])):
     getattr(_lib, _n).argtypes = _a
@@ -423,3 +567,82 @@ def iwht4x4_add_batch(dqcoeff, jobs, dst, bit_depth, stream=None):
     _check(_lib.lavish_iwht4x4_add_batch(_d(dqcoeff), _d(jobs), nj, _d(dst), dst.stride(0),
                                          bit_depth, int(dst.element_size() == 2),
                                          _stream_ptr(stream)), "lavish_iwht4x4_add_batch")
+
+
+# --------------------------- masked / OBMC / distance-weighted batch layer --
+def comp_jobs_tensor(jobs, device):
+    """Upload a COMP_JOB_DTYPE numpy array (LavishCompJob) as a device byte tensor."""
+    import torch
+    assert jobs.dtype == COMP_JOB_DTYPE
+    return torch.from_numpy(np.ascontiguousarray(jobs).view(np.uint8).copy()).to(device)
+
+
+def _as_u32(t):
+    import torch
+    return t.to(torch.int64) & 0xFFFFFFFF
+
+
+def comp_sad_batch(src, ref, w, h, jobs, nrefs=1, mode=0, second_pred=None, mask=None,
+                   fwd_offset=0, bck_offset=0, out=None, stream=None):
+    """mode 0: masked SAD (mask: 2-D uint8 device tensor), 1: distance-weighted
+    avg SAD.  second_pred: 1-D tensor of w x h blocks.  Returns [njobs, nrefs]
+    int64; `out` (int32, >= njobs * nrefs words) receives the raw words."""
+    import torch
+    highbd = src.element_size() == 2
+    nj = jobs.numel() // COMP_JOB_DTYPE.itemsize
+    if out is None:
+        out = torch.empty(nj * nrefs, dtype=torch.int32, device=src.device)
+    _check(_lib.lavish_comp_sad_batch(
+        _d(src), src.stride(0), _d(ref), ref.stride(0), w, h, _d(jobs), nj, nrefs, mode,
+        _d(second_pred), _d(mask), mask.stride(0) if mask is not None else 0, fwd_offset,
+        bck_offset, int(highbd), _d(out), _stream_ptr(stream)), "lavish_comp_sad_batch")
+    return _as_u32(out[:nj * nrefs]).reshape(nj, nrefs)
+
+
+def comp_variance_batch(a, b, w, h, jobs, kind=0, bit_depth=8, second_pred=None, mask=None,
+                        fwd_offset=0, bck_offset=0, var_out=None, sse_out=None, stream=None):
+    """kind 0: masked sub-pixel variance, 1: distance-weighted sub-pixel avg
+    variance of the filtered `a` against `b`.  Returns (var, sse) int64 [njobs]."""
+    import torch
+    highbd = a.element_size() == 2
+    nj = jobs.numel() // COMP_JOB_DTYPE.itemsize
+    if var_out is None:
+        var_out = torch.empty(nj, dtype=torch.int32, device=a.device)
+    if sse_out is None:
+        sse_out = torch.empty(nj, dtype=torch.int32, device=a.device)
+    _check(_lib.lavish_comp_variance_batch(
+        _d(a), a.stride(0), _d(b), b.stride(0), w, h, _d(jobs), nj, kind, bit_depth, int(highbd),
+        _d(second_pred), _d(mask), mask.stride(0) if mask is not None else 0, fwd_offset,
+        bck_offset, _d(var_out), _d(sse_out), _stream_ptr(stream)), "lavish_comp_variance_batch")
+    return _as_u32(var_out[:nj]), _as_u32(sse_out[:nj])
+
+
+def obmc_batch(pre, w, h, jobs, wsrc, mask, npre=1, kind=0, bit_depth=8, out=None, sse_out=None,
+               stream=None):
+    """kind 0: OBMC SAD [njobs, npre]; 1 / 2: (variance, sse) [njobs] of the
+    (bilinear-filtered) predictor.  wsrc / mask: 1-D int32 device tensors."""
+    import torch
+    highbd = pre.element_size() == 2
+    nj = jobs.numel() // COMP_JOB_DTYPE.itemsize
+    if out is None:
+        out = torch.empty(nj * npre, dtype=torch.int32, device=pre.device)
+    if sse_out is None:
+        sse_out = torch.empty(nj, dtype=torch.int32, device=pre.device)
+    _check(_lib.lavish_obmc_batch(_d(pre), pre.stride(0), w, h, _d(jobs), nj, npre, kind,
+                                  bit_depth, int(highbd), _d(wsrc), _d(mask), _d(out),
+                                  _d(sse_out), _stream_ptr(stream)), "lavish_obmc_batch")
+    if kind == 0:
+        return _as_u32(out[:nj * npre]).reshape(nj, npre)
+    return _as_u32(out[:nj]), _as_u32(sse_out[:nj])
+
+
+def comp_pred_batch(comp_pred, pred, w, h, ref, jobs, mode=0, mask=None, fwd_offset=0,
+                    bck_offset=0, stream=None):
+    """mode 0: avg, 1: distance-weighted, 2: mask.  comp_pred / pred: 1-D
+    tensors of contiguous w x h blocks; ref: 2-D plane.  In place on comp_pred."""
+    highbd = ref.element_size() == 2
+    nj = jobs.numel() // COMP_JOB_DTYPE.itemsize
+    _check(_lib.lavish_comp_pred_batch(
+        _d(comp_pred), _d(pred), w, h, _d(ref), ref.stride(0), _d(jobs), nj, mode, _d(mask),
+        mask.stride(0) if mask is not None else 0, fwd_offset, bck_offset, int(highbd),
+        _stream_ptr(stream)), "lavish_comp_pred_batch")

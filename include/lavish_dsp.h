@@ -344,6 +344,84 @@ int lavish_sum_sse_batch(const int16_t *src, int stride, int w, int h,
                          const LavishPixJob *jobs, int njobs, int32_t *sum,
                          int64_t *sse, void *stream);
 
+/* ---- compound pixel kernels: masked, OBMC, distance-weighted -------------
+ * The msdf / msvf / osdf / ovf / osvf / jsdaf / jsvaf members of
+ * aom_variance_fn_ptr_t (aom_dsp/variance.h:84-103) and the prediction
+ * helpers they reduce to.  One job = one block; offsets in ELEMENTS of the
+ * array they index.  (w, h) must be one of the 22 encoder block sizes.
+ *   blend      AOM_BLEND_A64(m, a, b) = (m*a + (64-m)*b + 32) >> 6
+ *   dist-wtd   (second*bck_offset + ref*fwd_offset + 8) >> 4, with
+ *              fwd_offset >= 0, bck_offset >= 0, fwd_offset + bck_offset == 16
+ *              (quant_dist_lookup_table, av1/common/common_data.h:421-426)
+ * Every call returns 0 for njobs <= 0 and a negative value, before any
+ * device work, for arguments it does not take.  The job record is 72 bytes. */
+typedef struct LavishCompJob {
+  int64_t src_off;     /* source block (comp_pred block for the pred call)        */
+  int64_t ref_off[4];  /* reference / predictor positions                          */
+  int64_t second_off;  /* second_pred block, stride w; OBMC: wsrc block (int32)    */
+  int64_t mask_off;    /* u8 mask block (mask_stride); OBMC: int32 mask block      */
+  int32_t xoff, yoff;  /* 1/8-pel bilinear offsets, 0..7                           */
+  int32_t invert_mask; /* masked modes: nonzero swaps the blend operands           */
+  int32_t reserved;
+} LavishCompJob;
+
+/* SAD of src against the compound prediction of each of nrefs (1..4) refs.
+ *   mode 0: masked (aom_dsp/sad_av1.c:21-67, highbd :95-133):
+ *           invert_mask == 0 -> blend(mask, ref, second_pred), else
+ *           blend(mask, second_pred, ref);
+ *        1: distance-weighted average (aom_dsp/sad.c:57-64, highbd :290-298).
+ *   sad_out[job * nrefs + k]. */
+int lavish_comp_sad_batch(const void *src, int src_stride, const void *ref,
+                          int ref_stride, int w, int h,
+                          const LavishCompJob *jobs, int njobs, int nrefs,
+                          int mode, const void *second_pred,
+                          const uint8_t *mask, int mask_stride, int fwd_offset,
+                          int bck_offset, int highbd, uint32_t *sad_out,
+                          void *stream);
+
+/* Variance of (bilinear-filtered a + job.src_off, reading (h+1) x (w+1),
+ * combined with second_pred) against b + job.ref_off[0].
+ *   kind 0: masked sub-pixel variance (aom_dsp/variance.c:749-814, highbd
+ *           :817-929), 1: distance-weighted sub-pixel avg variance
+ *           (variance.c:165-181, highbd to :664).
+ *   bit_depth 8/10/12 selects the highbd rounding (highbd = 1 only).
+ * Either output may be NULL. */
+int lavish_comp_variance_batch(const void *a, int a_stride, const void *b,
+                               int b_stride, int w, int h,
+                               const LavishCompJob *jobs, int njobs, int kind,
+                               int bit_depth, int highbd,
+                               const void *second_pred, const uint8_t *mask,
+                               int mask_stride, int fwd_offset, int bck_offset,
+                               uint32_t *var_out, uint32_t *sse_out,
+                               void *stream);
+
+/* OBMC: wsrc + job.second_off and mask + job.mask_off are contiguous w x h
+ * int32 blocks; pre + job.ref_off[k] is the predictor.
+ *   kind 0: SAD (aom_dsp/sad_av1.c:163-186, highbd :215-239) against npre
+ *           (1..4) predictors, out[job * npre + k];
+ *        1: variance (aom_dsp/variance.c:933-961, highbd :1040-1123),
+ *           out[job] = variance, sse_out[job] (may be NULL);
+ *        2: as 1 on the bilinear-filtered predictor (job.xoff / yoff).
+ *   npre must be 1 unless kind is 0. */
+int lavish_obmc_batch(const void *pre, int pre_stride, int w, int h,
+                      const LavishCompJob *jobs, int njobs, int npre, int kind,
+                      int bit_depth, int highbd, const int32_t *wsrc,
+                      const int32_t *mask, uint32_t *out, uint32_t *sse_out,
+                      void *stream);
+
+/* comp_pred + job.src_off (contiguous w x h) from pred + job.second_off
+ * (contiguous w x h) and ref + job.ref_off[0] (ref_stride).
+ *   mode 0: aom_comp_avg_pred, 1: aom_dist_wtd_comp_avg_pred,
+ *        2: aom_comp_mask_pred (invert_mask == 0 -> blend(mask, ref, pred))
+ *   (aom_dsp/variance.c:285-318, 707-767, 817-837).  Jobs of one call must not
+ *   overlap in comp_pred. */
+int lavish_comp_pred_batch(void *comp_pred, const void *pred, int w, int h,
+                           const void *ref, int ref_stride,
+                           const LavishCompJob *jobs, int njobs, int mode,
+                           const uint8_t *mask, int mask_stride,
+                           int fwd_offset, int bck_offset, int highbd,
+                           void *stream);
+
 /* ---- lossless 4x4 Walsh-Hadamard ----------------------------------------
  * av1_fwht4x4 (hybrid_fwd_txfm.c:24-76): src_diff + job.src_off (stride) ->
  * 16 words at coeff + job.aux_off. */
@@ -1145,6 +1223,101 @@ LAVISH_HBD_INV(32, 8) LAVISH_HBD_INV(16, 64) LAVISH_HBD_INV(64, 16)
 
 LAVISH_ENCODER_BLOCK_SIZES(LAVISH_SAD_PROTOS)
 LAVISH_ENCODER_BLOCK_SIZES(LAVISH_VAR_PROTOS)
+
+/* layout mirror of DIST_WTD_COMP_PARAMS (av1/common/blockd.h:554-558) */
+typedef struct LavishDistWtdCompParams {
+  int use_dist_wtd_comp_avg;
+  int fwd_offset;
+  int bck_offset;
+} LavishDistWtdCompParams;
+
+/* masked / OBMC / distance-weighted SAD: aom_dsp_rtcd_defs.pl:767, 889, 963,
+ * 970, 981, 990, 1007 */
+#define LAVISH_COMP_SAD_PROTOS(w, h)                                          \
+  unsigned int aom_masked_sad##w##x##h##_hip(                                 \
+      const uint8_t *src, int src_stride, const uint8_t *ref, int ref_stride, \
+      const uint8_t *second_pred, const uint8_t *msk, int msk_stride,         \
+      int invert_mask);                                                       \
+  void aom_masked_sad##w##x##h##x4d_hip(                                      \
+      const uint8_t *src, int src_stride, const uint8_t *ref[4],              \
+      int ref_stride, const uint8_t *second_pred, const uint8_t *msk,         \
+      int msk_stride, int invert_mask, unsigned sads[4]);                     \
+  unsigned int aom_highbd_masked_sad##w##x##h##_hip(                          \
+      const uint8_t *src8, int src_stride, const uint8_t *ref8,               \
+      int ref_stride, const uint8_t *second_pred8, const uint8_t *msk,        \
+      int msk_stride, int invert_mask);                                       \
+  unsigned int aom_obmc_sad##w##x##h##_hip(const uint8_t *pre, int pre_stride, \
+                                           const int32_t *wsrc,               \
+                                           const int32_t *mask);              \
+  unsigned int aom_highbd_obmc_sad##w##x##h##_hip(                            \
+      const uint8_t *pre, int pre_stride, const int32_t *wsrc,                \
+      const int32_t *mask);                                                   \
+  unsigned int aom_dist_wtd_sad##w##x##h##_avg_hip(                           \
+      const uint8_t *src_ptr, int src_stride, const uint8_t *ref_ptr,         \
+      int ref_stride, const uint8_t *second_pred,                             \
+      const LavishDistWtdCompParams *jcp_param);                              \
+  unsigned int aom_highbd_dist_wtd_sad##w##x##h##_avg_hip(                    \
+      const uint8_t *src_ptr, int src_stride, const uint8_t *ref_ptr,         \
+      int ref_stride, const uint8_t *second_pred,                             \
+      const LavishDistWtdCompParams *jcp_param);
+
+/* masked / distance-weighted sub-pixel variance: aom_dsp_rtcd_defs.pl:1366,
+ * 1513, 1522, 1530 (pre: aom_, aom_highbd_8_, aom_highbd_10_, aom_highbd_12_) */
+#define LAVISH_COMP_VAR_PROTOS_BD(pre, w, h)                                  \
+  unsigned int pre##masked_sub_pixel_variance##w##x##h##_hip(                 \
+      const uint8_t *src, int src_stride, int xoffset, int yoffset,           \
+      const uint8_t *ref, int ref_stride, const uint8_t *second_pred,         \
+      const uint8_t *msk, int msk_stride, int invert_mask,                    \
+      unsigned int *sse);                                                     \
+  uint32_t pre##dist_wtd_sub_pixel_avg_variance##w##x##h##_hip(               \
+      const uint8_t *src_ptr, int source_stride, int xoffset, int yoffset,    \
+      const uint8_t *ref_ptr, int ref_stride, uint32_t *sse,                  \
+      const uint8_t *second_pred, const LavishDistWtdCompParams *jcp_param);
+/* OBMC variance: aom_dsp_rtcd_defs.pl:1542-1543, 1552-1553 (pre: aom_,
+ * aom_highbd_, aom_highbd_10_, aom_highbd_12_) */
+#define LAVISH_OBMC_VAR_PROTOS_BD(pre, w, h)                                  \
+  unsigned int pre##obmc_variance##w##x##h##_hip(                             \
+      const uint8_t *pre_, int pre_stride, const int32_t *wsrc,               \
+      const int32_t *mask, unsigned int *sse);                                \
+  unsigned int pre##obmc_sub_pixel_variance##w##x##h##_hip(                   \
+      const uint8_t *pre_, int pre_stride, int xoffset, int yoffset,          \
+      const int32_t *wsrc, const int32_t *mask, unsigned int *sse);
+#define LAVISH_COMP_VAR_PROTOS(w, h)                  \
+  LAVISH_COMP_VAR_PROTOS_BD(aom_, w, h)               \
+  LAVISH_COMP_VAR_PROTOS_BD(aom_highbd_8_, w, h)      \
+  LAVISH_COMP_VAR_PROTOS_BD(aom_highbd_10_, w, h)     \
+  LAVISH_COMP_VAR_PROTOS_BD(aom_highbd_12_, w, h)     \
+  LAVISH_OBMC_VAR_PROTOS_BD(aom_, w, h)               \
+  LAVISH_OBMC_VAR_PROTOS_BD(aom_highbd_, w, h)        \
+  LAVISH_OBMC_VAR_PROTOS_BD(aom_highbd_10_, w, h)     \
+  LAVISH_OBMC_VAR_PROTOS_BD(aom_highbd_12_, w, h)
+
+LAVISH_ENCODER_BLOCK_SIZES(LAVISH_COMP_SAD_PROTOS)
+LAVISH_ENCODER_BLOCK_SIZES(LAVISH_COMP_VAR_PROTOS)
+
+/* compound prediction helpers: aom_dsp_rtcd_defs.pl:1602-1606, 1772-1775,
+ * 2029-2034.  (width, height) must be one of the 22 encoder block sizes. */
+void aom_comp_avg_pred_hip(uint8_t *comp_pred, const uint8_t *pred, int width,
+                           int height, const uint8_t *ref, int ref_stride);
+void aom_dist_wtd_comp_avg_pred_hip(uint8_t *comp_pred, const uint8_t *pred,
+                                    int width, int height, const uint8_t *ref,
+                                    int ref_stride,
+                                    const LavishDistWtdCompParams *jcp_param);
+void aom_comp_mask_pred_hip(uint8_t *comp_pred, const uint8_t *pred, int width,
+                            int height, const uint8_t *ref, int ref_stride,
+                            const uint8_t *mask, int mask_stride,
+                            int invert_mask);
+void aom_highbd_comp_avg_pred_hip(uint8_t *comp_pred8, const uint8_t *pred8,
+                                  int width, int height, const uint8_t *ref8,
+                                  int ref_stride);
+void aom_highbd_dist_wtd_comp_avg_pred_hip(
+    uint8_t *comp_pred8, const uint8_t *pred8, int width, int height,
+    const uint8_t *ref8, int ref_stride,
+    const LavishDistWtdCompParams *jcp_param);
+void aom_highbd_comp_mask_pred_hip(uint8_t *comp_pred, const uint8_t *pred8,
+                                   int width, int height, const uint8_t *ref8,
+                                   int ref_stride, const uint8_t *mask,
+                                   int mask_stride, int invert_mask);
 
 /* aom_dsp_rtcd_defs.pl:1303-1318,1326-1333 */
 #define LAVISH_MSE_PROTOS(pre)                                                 \
