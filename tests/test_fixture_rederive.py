@@ -93,3 +93,54 @@ def test_txfeat_rederived(G):
         np.testing.assert_array_equal(got, F["features"][k][32:34])
         done += 1
     assert done >= 5
+
+
+def test_interp_extremes_rederived():
+    """fix_interp_extremes: the three MULTITAP_SHARP2 cases per bit depth whose
+    int16 intermediate wraps (av1_highbd_convolve_2d_sr_c,
+    av1_highbd_dist_wtd_convolve_2d_c, av1_highbd_convolve_2d_scale_c at the
+    kernel's extreme phase), the lowbd scaled case whose uint16 sum wraps, and
+    a warp case on filter row 127, re-executed on the stored inputs."""
+    sys.path.insert(0, GOLD)
+    import gen_fix_interp_extremes as GX
+    import _extfix as E
+    import _extremes as X
+    F = E.load()
+    J = {n: i for i, n in enumerate(E.CONV_FIELDS)}
+    R = F["conv_rows"]
+    pe = X.extreme_phase(X.SHARP2)
+    picks = []
+    for unit, mode in ((E.SINGLE, 0), (E.COMPOUND, 1), (E.SCALE, 0)):
+        for bd in (10, 12):
+            m = [k for k in F["wrap_rows"] if tuple(R[k][[J[n] for n in (
+                "unit", "mode", "bd", "phase_x", "phase_y", "kind_y")]]) ==
+                (unit, mode, bd, pe, pe, X.SHARP2)]
+            assert m, (unit, bd)
+            picks.append(m[0])
+    m = np.flatnonzero((R[:, J["unit"]] == E.SCALE) & (R[:, J["highbd"]] == 0) &
+                       (R[:, J["kind_x"]] == X.SHARP2) & (R[:, J["phase_x"]] == pe) &
+                       (R[:, J["polarity"]] == 0) & (R[:, J["mode"]] == 0) &
+                       (R[:, J["aligned"]] == 1))
+    picks.append(int(m[0]))
+    cv = GX.Conv(GX.tu_convolve())
+    for k in picks:
+        c = E.conv_case(F, k)
+        v, got = E.conv_anchor(c)
+        assert v["wraps"] and got != v["final"] & 0xFFFF, k
+        cv.add(c.unit, c.highbd, c.bd, c.w, c.h, c.path, (c.kind_x, c.kind_y),
+               (c.phase_x, c.phase_y), c.polarity, mode=c.mode,
+               steps=(c.x_step_qn, c.y_step_qn), subpel=(c.subpel_x_qn, c.subpel_y_qn),
+               src=c.src.astype(np.int64), org=(c.org_y, c.org_x))
+        np.testing.assert_array_equal(cv.dst[-1].reshape(c.h, c.w), c.dst, err_msg=str(k))
+        np.testing.assert_array_equal(cv.buf[-1].reshape(c.h, c.w), c.buf, err_msg=str(k))
+    WJ = {n: i for i, n in enumerate(E.WARP_FIELDS)}
+    Wr = F["warp_rows"]
+    wp = GX.Warp(GX.tu_warp())
+    for mode in (0, 1):
+        k = int(np.flatnonzero((Wr[:, WJ["row_x"]] == 127) & (Wr[:, WJ["bd"]] == 10) &
+                               (Wr[:, WJ["mode"]] == mode) & (Wr[:, WJ["polarity"]] == 1))[0])
+        c = E.warp_case(F, k)
+        wp.add(c.bd, c.mode, c.polarity, c.ref.astype(np.int64), c.mat, c.prm, c.p_col, c.p_row,
+               c.p_width, c.p_height)
+        np.testing.assert_array_equal(wp.pred[-1].reshape(c.pred.shape), c.pred, err_msg=str(k))
+        np.testing.assert_array_equal(wp.buf[-1].reshape(c.buf.shape), c.buf, err_msg=str(k))
