@@ -530,6 +530,26 @@ def block_error_batch(coeff, dqcoeff, bit_depth=0, stream=None):
     return err, ssz
 
 
+def satd_lp_batch(coeff, stream=None):
+    """aom_satd_lp over int16 rows [nblocks, length]."""
+    import torch
+    nb, length = coeff.shape
+    out = torch.empty(nb, dtype=torch.int32, device=coeff.device)
+    _check(_lib.lavish_satd_lp_batch(_d(coeff), length, nb, _d(out), _stream_ptr(stream)),
+           "lavish_satd_lp_batch")
+    return out
+
+
+def block_error_lp_batch(coeff, dqcoeff, stream=None):
+    """av1_block_error_lp over int16 rows [nblocks, n]."""
+    import torch
+    nb, n = coeff.shape
+    err = torch.empty(nb, dtype=torch.int64, device=coeff.device)
+    _check(_lib.lavish_block_error_lp_batch(_d(coeff), _d(dqcoeff), n, nb, _d(err),
+                                            _stream_ptr(stream)), "lavish_block_error_lp_batch")
+    return err
+
+
 def sum_sse_batch(src, w, h, jobs, stream=None):
     """(sum int32, sse int64) tensors of lavish_sum_sse_batch."""
     import torch
