@@ -7,6 +7,7 @@
 
 #include "lavish_internal.h"
 #include "qlookup_tables.h"
+#include "shim_stage.h"
 
 namespace lavish {
 
@@ -337,26 +338,19 @@ static void fwd2d_shim(int tx_size, const int16_t* input, int32_t* output, int s
     shim_reject("av1_fwd_txfm2d (tx_size / tx_type)", -5);
     return;
   }
-  hipStream_t s = shim_stream();
   const int n = max_eob(tx_size);
-  const size_t in_bytes = (size_t)H * W * sizeof(int16_t);
-  const size_t in_pad = (in_bytes + 255) & ~(size_t)255;
-  char* scratch = (char*)shim_scratch(in_pad + (size_t)n * sizeof(int32_t));
-  int16_t* din = (int16_t*)scratch;
-  int32_t* dout = (int32_t*)(scratch + in_pad);
+  Stage st(Stage::pad((size_t)H * W * sizeof(int16_t)) + Stage::pad((size_t)n * sizeof(int32_t)));
   // only the H x W window of the caller's rows is read
-  LAVISH_CHECK(hipMemcpy2DAsync(din, (size_t)W * sizeof(int16_t), input,
-                                (size_t)stride * sizeof(int16_t), (size_t)W * sizeof(int16_t), H,
-                                hipMemcpyHostToDevice, s));
+  const int16_t* din = st.block(input, stride, W, H);
+  int32_t* dout = st.take_n<int32_t>(n);
   const int rc = txq_plane(din, W, W, H, tx_size, 1u << tx_type, 8, LAVISH_QUANT_NONE, nullptr,
-                           nullptr, nullptr, nullptr, dout, s);
+                           nullptr, nullptr, nullptr, dout, st.s);
   if (rc != 0) {
     shim_reject("txq_plane", rc);
     return;
   }
-  LAVISH_CHECK(hipMemcpyAsync(output, dout, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost,
-                              s));
-  LAVISH_CHECK(hipStreamSynchronize(s));
+  st.copy_out(output, dout, (size_t)n);
+  st.sync();
   // 64-point sizes: the reference zeroes and re-packs in place
   // (av1_fwd_txfm2d.c:248-311), which leaves, past the n packed words, the
   // original copies of columns KW/2..KW-1 (rows < 32) of a 64-high buffer
@@ -441,22 +435,18 @@ static void quant_shim(const int32_t* coeff, intptr_t n, const int16_t* zbin,
     qp.quant_shift[i] = qshift ? qshift[i] : 0;
     qp.dequant[i] = dequant[i];
   }
-  hipStream_t s = shim_stream();
-  const size_t cb = (size_t)n * sizeof(int32_t);
-  const size_t sb = ((size_t)n * sizeof(int16_t) + 255) & ~(size_t)255;
-  char* base = (char*)shim_scratch(3 * cb + sb + 256);
-  int32_t* dc = (int32_t*)base;
-  int32_t* dq = (int32_t*)(base + cb);
-  int32_t* ddq = (int32_t*)(base + 2 * cb);
-  int16_t* dscan = (int16_t*)(base + 3 * cb);
-  uint16_t* deob = (uint16_t*)(base + 3 * cb + sb);
-  LAVISH_CHECK(hipMemcpyAsync(dc, coeff, cb, hipMemcpyHostToDevice, s));
-  LAVISH_CHECK(hipMemcpyAsync(dscan, scan, (size_t)n * sizeof(int16_t), hipMemcpyHostToDevice, s));
-  quantize_batch(dc, (int)n, 1, dscan, log_scale, bd, kind, &qp, dq, ddq, deob, s);
-  LAVISH_CHECK(hipMemcpyAsync(qcoeff, dq, cb, hipMemcpyDeviceToHost, s));
-  LAVISH_CHECK(hipMemcpyAsync(dqcoeff, ddq, cb, hipMemcpyDeviceToHost, s));
-  LAVISH_CHECK(hipMemcpyAsync(eob, deob, sizeof(uint16_t), hipMemcpyDeviceToHost, s));
-  LAVISH_CHECK(hipStreamSynchronize(s));
+  Stage st(3 * Stage::pad((size_t)n * sizeof(int32_t)) + Stage::pad((size_t)n * sizeof(int16_t)) +
+           Stage::pad(sizeof(uint16_t)));
+  const int32_t* dc = st.copy_in(coeff, (size_t)n);
+  int32_t* dq = st.take_n<int32_t>(n);
+  int32_t* ddq = st.take_n<int32_t>(n);
+  const int16_t* dscan = st.copy_in(scan, (size_t)n);
+  uint16_t* deob = st.take_n<uint16_t>(1);
+  quantize_batch(dc, (int)n, 1, dscan, log_scale, bd, kind, &qp, dq, ddq, deob, st.s);
+  st.copy_out(qcoeff, dq, (size_t)n);
+  st.copy_out(dqcoeff, ddq, (size_t)n);
+  st.copy_out(eob, deob, 1);
+  st.sync();
 }
 
 #define QUANT_SHIM(name, ls, kind, bd)                                                   \

@@ -20,14 +20,12 @@
 // arguments.
 #include <algorithm>
 
-#include "lavish_internal.h"
-
+#include "conv_dev.h"
+#include "shim_stage.h"
 
 namespace lavish {
 namespace {
 
-constexpr int kFBits = 7;   // FILTER_BITS
-constexpr int kMaxTaps = 12;
 constexpr int kMaxW = 128, kMaxH = 128;
 
 struct CompArgs {
@@ -36,10 +34,9 @@ struct CompArgs {
   uint16_t* conv;
   const LavishCompoundJob* jobs;
   int src_stride, dst_stride, conv_stride, w, h, njobs, bd;
-  int tx, ty;                           // tap counts
   int lw, bpw, any2d;                   // log2(w), blocks per workgroup, 2-D path possible
-  int16_t fx[16][kMaxTaps], fy[16][kMaxTaps];
-  int r0, r1, offset_bits, round_offset, round_bits, do_average, dist_wtd, fwd, bck;
+  ConvTaps taps;
+  ConvRound rnd;
 };
 
 // a.bpw blocks per 256-thread workgroup (small blocks share one), each with
@@ -49,8 +46,7 @@ struct CompArgs {
 template <typename Pix, bool T8>
 __global__ __launch_bounds__(256) void compound_kernel(CompArgs a) {
   extern __shared__ int16_t im_all[];
-  const int nwg = gridDim.x;  // multiple of 8: consecutive blocks share an XCD's L2
-  const int wg = (blockIdx.x & 7) * (nwg >> 3) + (blockIdx.x >> 3);
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int tpb = 256 / a.bpw;  // threads per block
   const int sub = threadIdx.x / tpb, t = threadIdx.x - sub * tpb;
   const int j = wg * a.bpw + sub;
@@ -62,11 +58,11 @@ __global__ __launch_bounds__(256) void compound_kernel(CompArgs a) {
   Pix* dst = (Pix*)a.dst + jb.dst_off;
   uint16_t* conv = a.conv + jb.conv_off;
   const int w = a.w, lw = a.lw;
-  const int ntx = T8 ? 8 : a.tx, nty = T8 ? 8 : a.ty;
+  const int ntx = T8 ? 8 : a.taps.tx, nty = T8 ? 8 : a.taps.ty;
   constexpr int kUnroll = T8 ? 8 : 1;  // full unroll of the T8 tap loops only
   const int fo_x = ntx / 2 - 1, fo_y = nty / 2 - 1;
-  const int16_t* fxp = a.fx[sx];
-  const int16_t* fyp = a.fy[sy];
+  const int16_t* fxp = a.taps.fx[sx];
+  const int16_t* fyp = a.taps.fy[sy];
   // T8: the block's two tap rows live in registers for all its pixels
   int16_t fx[T8 ? 8 : 1], fy[T8 ? 8 : 1];
   if (T8) {
@@ -78,7 +74,7 @@ __global__ __launch_bounds__(256) void compound_kernel(CompArgs a) {
   }
 #define FX(k) (T8 ? fx[(k) & (T8 ? 7 : 0)] : fxp[k])
 #define FY(k) (T8 ? fy[(k) & (T8 ? 7 : 0)] : fyp[k])
-  int16_t* im = im_all + sub * (a.h + a.ty - 1) * w;
+  int16_t* im = im_all + sub * (a.h + a.taps.ty - 1) * w;
   if (a.any2d) {  // horizontal pass of the 2-D form into LDS (w is a power of two)
     if (path == 3) {
       const int ih = a.h + nty - 1;
@@ -88,7 +84,7 @@ __global__ __launch_bounds__(256) void compound_kernel(CompArgs a) {
         int32_t s = 1 << (a.bd + kFBits - 1);
 #pragma unroll kUnroll
         for (int k = 0; k < ntx; ++k) s += FX(k) * (int)row[k];
-        im[e] = (int16_t)((s + ((1 << a.r0) >> 1)) >> a.r0);
+        im[e] = (int16_t)((s + ((1 << a.rnd.r0) >> 1)) >> a.rnd.r0);
       }
     }
     __syncthreads();
@@ -99,36 +95,34 @@ __global__ __launch_bounds__(256) void compound_kernel(CompArgs a) {
     const int y = e >> lw, x = e & (w - 1);
     int32_t res;
     if (path == 0) {
-      res = (uint16_t)(((int)src[(int64_t)y * a.src_stride + x] << a.round_bits) +
-                       a.round_offset);
+      res = (uint16_t)(((int)src[(int64_t)y * a.src_stride + x] << a.rnd.round_bits) +
+                       a.rnd.round_offset);
     } else if (path == 1) {
       const Pix* row = src + (int64_t)y * a.src_stride + x - fo_x;
       int32_t s = 0;
 #pragma unroll kUnroll
       for (int k = 0; k < ntx; ++k) s += FX(k) * (int)row[k];
-      res = (1 << (kFBits - a.r1)) * ((s + ((1 << a.r0) >> 1)) >> a.r0) + a.round_offset;
+      res = (1 << (kFBits - a.rnd.r1)) * ((s + ((1 << a.rnd.r0) >> 1)) >> a.rnd.r0) +
+            a.rnd.round_offset;
     } else if (path == 2) {
       const Pix* col = src + (int64_t)(y - fo_y) * a.src_stride + x;
       int32_t s = 0;
 #pragma unroll kUnroll
       for (int k = 0; k < nty; ++k) s += FY(k) * (int)col[(int64_t)k * a.src_stride];
-      s *= 1 << (kFBits - a.r0);
-      res = ((s + ((1 << a.r1) >> 1)) >> a.r1) + a.round_offset;
+      s *= 1 << (kFBits - a.rnd.r0);
+      res = ((s + ((1 << a.rnd.r1) >> 1)) >> a.rnd.r1) + a.rnd.round_offset;
     } else {
-      int32_t s = 1 << a.offset_bits;
+      int32_t s = 1 << a.rnd.offset_bits;
 #pragma unroll kUnroll
       for (int k = 0; k < nty; ++k) s += FY(k) * (int)im[((y + k) << lw) + x];
-      res = (uint16_t)((s + ((1 << a.r1) >> 1)) >> a.r1);
+      res = (uint16_t)((s + ((1 << a.rnd.r1) >> 1)) >> a.rnd.r1);
     }
     uint16_t* c = conv + (int64_t)y * a.conv_stride + x;
-    if (!a.do_average) {
+    if (!a.rnd.do_average) {
       *c = (uint16_t)res;
       continue;
     }
-    int32_t tt = *c;
-    tt = a.dist_wtd ? (tt * a.fwd + res * a.bck) >> 4 : (tt + res) >> 1;
-    tt -= a.round_offset;
-    const int v = (tt + ((1 << a.round_bits) >> 1)) >> a.round_bits;
+    const int v = conv_average(a.rnd, *c, res);
     dst[(int64_t)y * a.dst_stride + x] = (Pix)min(max(v, 0), pmax);
   }
 #undef FX
@@ -144,15 +138,13 @@ int compound_batch(const void* src, int src_stride, void* dst, int dst_stride, u
   if (njobs <= 0) return 0;
   if (!src || !conv || !jobs || !cp || !fpx || !fpy || (cp->do_average && !dst)) return -1;
   if (w < 2 || h < 1 || w > kMaxW || h > kMaxH || (w & (w - 1))) return -2;
-  if (highbd ? (bd != 8 && bd != 10 && bd != 12) : bd != 8) return -3;
-  if (fpx->taps < 2 || fpx->taps > kMaxTaps || fpy->taps < 2 || fpy->taps > kMaxTaps ||
-      (fpx->taps & 1) || (fpy->taps & 1) || !fpx->filter_ptr || !fpy->filter_ptr)
-    return -4;
-  const int round_bits = 2 * kFBits - cp->round_0 - cp->round_1;
-  if (cp->round_0 < 0 || cp->round_1 < 0 || round_bits < 0 || cp->round_1 > kFBits ||
-      cp->round_0 > kFBits)
-    return -5;
+  if (!bd_ok(bd, highbd)) return -3;
   CompArgs a{};
+  if (!conv_taps(fpx, fpy, a.taps)) return -4;
+  // (both <= FILTER_BITS: round_bits >= 0)
+  if (cp->round_0 < 0 || cp->round_1 < 0 || cp->round_0 > kFBits || cp->round_1 > kFBits)
+    return -5;
+  a.rnd = conv_round(*cp, bd);
   a.src = src;
   a.dst = dst;
   a.conv = conv;
@@ -164,30 +156,13 @@ int compound_batch(const void* src, int src_stride, void* dst, int dst_stride, u
   a.h = h;
   a.njobs = njobs;
   a.bd = bd;
-  a.tx = fpx->taps;
-  a.ty = fpy->taps;
-  for (int p = 0; p < 16; ++p)  // av1_get_interp_filter_subpel_kernel rows
-    for (int k = 0; k < kMaxTaps; ++k) {
-      a.fx[p][k] = k < a.tx ? fpx->filter_ptr[a.tx * p + k] : 0;
-      a.fy[p][k] = k < a.ty ? fpy->filter_ptr[a.ty * p + k] : 0;
-    }
-  a.r0 = cp->round_0;
-  a.r1 = cp->round_1;
-  a.offset_bits = bd + 2 * kFBits - cp->round_0;
-  a.round_offset = (1 << (a.offset_bits - cp->round_1)) + (1 << (a.offset_bits - cp->round_1 - 1));
-  a.round_bits = round_bits;
-  a.do_average = cp->do_average;
-  a.dist_wtd = cp->use_dist_wtd_comp_avg;
-  a.fwd = cp->fwd_offset;
-  a.bck = cp->bck_offset;
   a.lw = 31 - __builtin_clz(w);
   // blocks of <= 256 pixels share a workgroup 4 ways, <= 1024 2 ways
   a.bpw = w * h <= 256 ? 4 : (w * h <= 1024 ? 2 : 1);
   a.any2d = 1;  // the per-block path is decided on the device
-  const size_t lds = (size_t)a.bpw * (h + a.ty - 1) * w * sizeof(int16_t);
-  int nwg = (njobs + a.bpw - 1) / a.bpw;
-  nwg = (nwg + 7) & ~7;
-  const bool t8 = a.tx == 8 && a.ty == 8;
+  const size_t lds = (size_t)a.bpw * (h + a.taps.ty - 1) * w * sizeof(int16_t);
+  const int nwg = xcd_grid((njobs + a.bpw - 1) / a.bpw);
+  const bool t8 = a.taps.tx == 8 && a.taps.ty == 8;
   if (highbd) {
     if (t8) hipLaunchKernelGGL((compound_kernel<uint16_t, true>), dim3(nwg), dim3(256), lds, s, a);
     else hipLaunchKernelGGL((compound_kernel<uint16_t, false>), dim3(nwg), dim3(256), lds, s, a);
@@ -231,38 +206,28 @@ void compound_shim(const Pix* src, int ss, Pix* dst, int ds, int w, int h,
   const int path = (sx & 15 ? 1 : 0) + (sy & 15 ? 2 : 0);
   const int mx = (path & 1) ? px->taps / 2 - 1 : 0, my = (path & 2) ? py->taps / 2 - 1 : 0;
   const int wx = w + ((path & 1) ? px->taps - 1 : 0), wy = h + ((path & 2) ? py->taps - 1 : 0);
-  const hipStream_t s = shim_stream();
-  const size_t sb = ((size_t)wx * wy * sizeof(Pix) + 255) & ~(size_t)255;
-  const size_t db = ((size_t)w * h * sizeof(Pix) + 255) & ~(size_t)255;
-  const size_t cb = ((size_t)w * h * 2 + 255) & ~(size_t)255;
-  char* base = (char*)shim_scratch(sb + db + cb + 256);
-  Pix* dsrc = (Pix*)base;
-  Pix* ddst = (Pix*)(base + sb);
-  uint16_t* dconv = (uint16_t*)(base + sb + db);
-  LavishCompoundJob* djob = (LavishCompoundJob*)(base + sb + db + cb);
-  LAVISH_CHECK(hipMemcpy2DAsync(dsrc, (size_t)wx * sizeof(Pix), src - (int64_t)my * ss - mx,
-                                (size_t)ss * sizeof(Pix), (size_t)wx * sizeof(Pix), wy,
-                                hipMemcpyHostToDevice, s));
-  LAVISH_CHECK(hipMemcpy2DAsync(dconv, (size_t)w * 2, cp->dst, (size_t)cp->dst_stride * 2,
-                                (size_t)w * 2, h, hipMemcpyHostToDevice, s));
+  const size_t n = (size_t)w * h;
+  Stage st(Stage::pad((size_t)wx * wy * sizeof(Pix)) + Stage::pad(n * sizeof(Pix)) +
+           Stage::pad(n * sizeof(uint16_t)) + Stage::pad(sizeof(LavishCompoundJob)));
+  const Pix* dsrc = st.block(src - (int64_t)my * ss - mx, ss, wx, wy);
+  Pix* ddst = st.take_n<Pix>(n);
+  uint16_t* dconv = st.block(cp->dst, cp->dst_stride, w, h);
   LavishCompoundJob jb{};
   jb.src_off = (int64_t)my * wx + mx;
   jb.subpel_x_qn = path & 1 ? sx : 0;
   jb.subpel_y_qn = path & 2 ? sy : 0;
-  LAVISH_CHECK(hipMemcpyAsync(djob, &jb, sizeof(jb), hipMemcpyHostToDevice, s));
+  const LavishCompoundJob* djob = st.copy_in(&jb, 1);
   const int rc = compound_batch(dsrc, wx, ddst, w, dconv, w, w, h, djob, 1, px, py, cp, bd,
-                                sizeof(Pix) == 2, s);
+                                sizeof(Pix) == 2, st.s);
   if (rc != 0) {
     shim_reject("av1_dist_wtd_convolve_hip", rc);
     return;
   }
   if (cp->do_average)
-    LAVISH_CHECK(hipMemcpy2DAsync(dst, (size_t)ds * sizeof(Pix), ddst, (size_t)w * sizeof(Pix),
-                                  (size_t)w * sizeof(Pix), h, hipMemcpyDeviceToHost, s));
+    st.block_out(dst, ds, ddst, w, h);
   else
-    LAVISH_CHECK(hipMemcpy2DAsync(cp->dst, (size_t)cp->dst_stride * 2, dconv, (size_t)w * 2,
-                                  (size_t)w * 2, h, hipMemcpyDeviceToHost, s));
-  LAVISH_CHECK(hipStreamSynchronize(s));
+    st.block_out(cp->dst, cp->dst_stride, dconv, w, h);
+  st.sync();
 }
 }  // namespace
 

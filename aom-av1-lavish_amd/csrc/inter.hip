@@ -273,10 +273,7 @@ template <typename T, int CW, int R, bool FAST>
 __global__ __launch_bounds__(256) void inter_kernel(IpArgs a) {
   const int ncg = a.w / CW;
   const int tpj = ncg * (a.h / R);
-  // XCD-aware: consecutive jobs (neighbouring blocks, overlapping source
-  // windows) land on the same XCD's L2
-  const int nwg = gridDim.x;  // multiple of 8
-  const int wg = (blockIdx.x & 7) * (nwg >> 3) + (blockIdx.x >> 3);
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const uint32_t gid = (uint32_t)wg * 256u + threadIdx.x;  // < 2^31 (host check)
   const uint32_t j = gid / (uint32_t)tpj;
   if (j >= (uint32_t)a.njobs) return;
@@ -423,7 +420,7 @@ void launch_cw(const IpArgs& a, hipStream_t s) {
               hipErrorInvalidValue, __FILE__, __LINE__);
     return;
   }
-  const int nwg = (int)(((threads + 255) / 256 + 7) & ~7LL);
+  const int nwg = xcd_grid((int)((threads + 255) / 256));
   if (fast) {
     if (R == 16)
       hipLaunchKernelGGL((inter_kernel<T, CW, 16, kFastOk>), dim3(nwg), dim3(256), 0, s, a);
@@ -472,7 +469,7 @@ int inter_pred_batch(const void* ref, int ref_stride, int ref_width, int ref_hei
                      const int16_t* custom, int r0, int r1, hipStream_t s) {
   if (!pow2_size(w) || !pow2_size(h)) return -3;
   if (ss_x < 0 || ss_x > 1 || ss_y < 0 || ss_y > 1) return -1;
-  if (highbd ? (bd != 8 && bd != 10 && bd != 12) : bd != 8) return -1;
+  if (!bd_ok(bd, highbd)) return -1;
   if (ref_width < 0 || ref_height < 0) return -4;
   if (njobs < 0) return -4;
   if (njobs == 0) return 0;

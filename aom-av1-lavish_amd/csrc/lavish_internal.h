@@ -142,6 +142,20 @@ struct StreamScratch {
   void release(hipStream_t s);
 };
 
+// the bit depths a batch entry point takes: 8 / 10 / 12 for u16 pixels, 8 for u8
+inline bool bd_ok(int bd, int highbd) {
+  return highbd ? (bd == 8 || bd == 10 || bd == 12) : bd == 8;
+}
+
+// XCD-aware workgroup order: the hardware deals workgroups round-robin over
+// the 8 XCDs, so workgroup id of a grid of n (= xcd_grid of the count needed:
+// the remap is a permutation only for a multiple of 8) takes job group
+// xcd_remap(id, n) and consecutive jobs share an XCD's L2
+inline int xcd_grid(int n) { return (n + 7) & ~7; }
+__device__ __forceinline__ int xcd_remap(uint32_t id, uint32_t n) {
+  return (int)((id & 7) * (n >> 3) + (id >> 3));
+}
+
 // Under-aligned word vectors for byte-addressed loads (pixel rows at any byte
 // offset).  aligned(1) makes no alignment promise to the compiler, so it
 // cannot split, merge or scalarise on an assumed 8 / 16-byte boundary; the

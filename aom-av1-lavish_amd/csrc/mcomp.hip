@@ -19,9 +19,7 @@ __global__ __launch_bounds__(64 * kDkWaves, (W <= 16 && H <= 16) ? 8 : 7) void d
                                                       LavishDiamondResult* __restrict__ out,
                                                       int32_t* __restrict__ cost_lists,
                                                       uint8_t* __restrict__ sdf_kind) {
-  // XCD-aware: consecutive job quads (neighbouring blocks) share an XCD's L2
-  const int nwg = gridDim.x;  // multiple of 8
-  const int wg = (blockIdx.x & 7) * (nwg >> 3) + (blockIdx.x >> 3);
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int j = wg * kDkWaves + wave;
@@ -190,8 +188,7 @@ void launch_tl(const uint8_t* src, int ss, const uint8_t* ref, int rs, const Lav
                const LavishDiamondJob* jobs, int njobs, int step_param,
                const LavishMvCostParams& cost, int skip, int method, LavishDiamondResult* out,
                int32_t* cost_lists, hipStream_t s, uint8_t* sdf_kind = nullptr) {
-  int nwg = (njobs + kDkWaves - 1) / kDkWaves;
-  nwg = (nwg + 7) & ~7;
+  const int nwg = xcd_grid((njobs + kDkWaves - 1) / kDkWaves);
   if (diamond_method(method))
     hipLaunchKernelGGL((diamond_kernel<W, H, false, TL>), dim3(nwg), dim3(64 * kDkWaves), 0, s, src, ss,
                        ref, rs, t, (const Job*)jobs, njobs, step_param, cost, skip, method, out,

@@ -367,8 +367,7 @@ __device__ __forceinline__ void lj_group(
     const LavishMvCostParams& cost, const int32_t* dec, int skip,
     LavishDiamondResult* __restrict__ out, int32_t* __restrict__ cost_lists, int vwg, int nvwg) {
   __shared__ uint32_t res_s[WPG][kLjJobs][kMaxSteps];  // (LDS-addressed, not through a pointer)
-  // XCD-aware: consecutive job groups (neighbouring blocks) share an XCD's L2
-  const int wg = (vwg & 7) * (nvwg >> 3) + (vwg >> 3);
+  const int wg = xcd_remap(vwg, nvwg);
   const int lane = threadIdx.x & 63;
   const int wave = WPG == 1 ? 0 : threadIdx.x >> 6;
   const int j0 = (wg * WPG + wave) * kLjJobs;
@@ -656,7 +655,7 @@ void launch_lj(const uint8_t* src, int ss, const uint8_t* ref, int rs, const Lav
                int32_t* cost_lists, hipStream_t s) {
   const int waves = (njobs + kLjJobs - 1) / kLjJobs;
   constexpr int wpg = 4;
-  const int nwg = (((waves + wpg - 1) / wpg) + 7) & ~7;
+  const int nwg = xcd_grid((waves + wpg - 1) / wpg);
   const int cap = lj_grid_cap();
   const int grid = cap > 0 && cap < nwg ? cap : nwg;
   // a capped grid pulls its units from the queues (diamond_lj_dyn_kernel)
@@ -700,7 +699,7 @@ extern "C" int lavish_set_search_schedule(int queued) {
 
 extern "C" int lavish_set_search_workgroup_cap(int workgroups) {
   if (workgroups < 0) return -1;
-  lavish::g_lj_cap.store((workgroups + 7) & ~7, std::memory_order_relaxed);
+  lavish::g_lj_cap.store(xcd_grid(workgroups), std::memory_order_relaxed);
   return 0;
 }
 
@@ -771,7 +770,7 @@ extern "C" int lavish_txq_frame_search(
   c.out = out;
   c.cost_lists = cost_lists;
   const int waves = (c.njobs + kLjJobs - 1) / kLjJobs;
-  c.nvwg = (((waves + 3) / 4) + 7) & ~7;
+  c.nvwg = xcd_grid((waves + 3) / 4);
   c.units = c.nvwg / 8;
   if (c.units > 0 && cost->mv_cost_type == 0) {
     c.dec = (const int32_t*)t_mvdec.acquire(2 * kMvDecN * sizeof(int32_t), s);

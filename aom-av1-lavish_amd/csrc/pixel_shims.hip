@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "lavish_internal.h"
+#include "shim_stage.h"
 
 namespace lavish {
 namespace {
@@ -17,44 +18,6 @@ template <typename T>
 T* untag(const uint8_t* p) {
   if constexpr (sizeof(T) == 2) return (T*)((uintptr_t)p << 1);
   else return (T*)p;
-}
-
-// bump allocator over the per-thread scratch for one shim call
-struct Stage {
-  char* base;
-  size_t used = 0;
-  hipStream_t s;
-  explicit Stage(size_t cap) : base((char*)shim_scratch(cap)), s(shim_stream()) {}
-  void* take(size_t bytes) {
-    void* p = base + used;
-    used += (bytes + 255) & ~(size_t)255;
-    return p;
-  }
-  // copy a w x h window (stride in elements) into a compact device block
-  template <typename T>
-  T* block(const T* host, ptrdiff_t stride, int w, int h) {
-    T* d = (T*)take((size_t)w * h * sizeof(T));
-    LAVISH_CHECK(hipMemcpy2DAsync(d, (size_t)w * sizeof(T), host, (size_t)stride * sizeof(T),
-                                  (size_t)w * sizeof(T), h, hipMemcpyHostToDevice, s));
-    return d;
-  }
-  template <typename T>
-  T* copy_in(const T* host, size_t n) {
-    T* d = (T*)take(n * sizeof(T));
-    LAVISH_CHECK(hipMemcpyAsync(d, host, n * sizeof(T), hipMemcpyHostToDevice, s));
-    return d;
-  }
-  template <typename T>
-  void copy_out(T* host, const T* dev, size_t n) {
-    LAVISH_CHECK(hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, s));
-  }
-  void sync() { LAVISH_CHECK(hipStreamSynchronize(s)); }
-};
-
-constexpr size_t kStageCap = 4u << 20;  // 128x128 u16 x (src + 4 refs + second) + outputs
-
-void must(int rc, const char* what) {
-  if (rc != 0) shim_reject(what, rc);
 }
 
 template <typename Pix>
@@ -369,8 +332,7 @@ void conv_shim(const Pix* src, ptrdiff_t ss, Pix* dst, ptrdiff_t ds, int w, int 
   must(inter_pred_batch(win, ww, 0, 0, 0, 0, w, h, djob, 1, nullptr, dout, w, bd,
                         sizeof(Pix) == 2, dc, r0, r1, st.s),
        "inter_pred_batch");
-  LAVISH_CHECK(hipMemcpy2DAsync(dst, (size_t)ds * sizeof(Pix), dout, (size_t)w * sizeof(Pix),
-                                (size_t)w * sizeof(Pix), h, hipMemcpyDeviceToHost, st.s));
+  st.block_out(dst, ds, dout, w, h);
   st.sync();
 }
 

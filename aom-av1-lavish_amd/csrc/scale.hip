@@ -28,15 +28,14 @@
 // caller's filters sit in LDS (32-byte rows: one ds_read_b128 per 8 taps).
 // Steps up to 2048 (the 2:1 downscale limit of av1_is_valid_scale) bound the
 // intermediate at 2 h + taps rows.
-#include "lavish_internal.h"
+#include "conv_dev.h"
+#include "shim_stage.h"
 
 namespace lavish {
 namespace {
 
-constexpr int kFBits = 7;      // FILTER_BITS
 constexpr int kScaleBits = 10; // SCALE_SUBPEL_BITS
 constexpr int kScaleExtra = 6; // SCALE_EXTRA_BITS
-constexpr int kMaxTaps = 12;
 constexpr int kMaxStep = 2048;
 
 struct ScaleArgs {
@@ -45,10 +44,9 @@ struct ScaleArgs {
   uint16_t* conv;
   const LavishScaleJob* jobs;
   int src_stride, dst_stride, conv_stride, w, h, lw, njobs, bd;
-  int tx, ty;
   int nb, im_cap;  // blocks per workgroup, int16 slots of one block's intermediate
-  int16_t fx[16][kMaxTaps], fy[16][kMaxTaps];
-  int r0, r1, offset_bits, round_offset, round_bits, is_compound, do_average, dist_wtd, fwd, bck;
+  ConvTaps taps;
+  ConvRound rnd;
 };
 
 constexpr int kFRow = 16;  // LDS kernel row stride (int16): 32 bytes
@@ -107,14 +105,14 @@ __global__ __launch_bounds__(256) void scale_kernel(ScaleArgs a) {
   const int t = threadIdx.x;
   for (int e = t; e < 2 * 16 * kFRow; e += 256) {
     const int tab = e / (16 * kFRow), r = (e / kFRow) & 15, k = e % kFRow;
-    lds[e] = k < kMaxTaps ? (tab ? a.fy[r][k] : a.fx[r][k]) : 0;
+    lds[e] = k < kMaxTaps ? (tab ? a.taps.fy[r][k] : a.taps.fx[r][k]) : 0;
   }
   const int nb = a.nb, tpb = 256 / nb;
   const int slot = t / tpb, tb = t - slot * tpb;
   const int job = blockIdx.x * nb + slot;
   int16_t* im = lds + 2 * 16 * kFRow + slot * a.im_cap;
   const int w = a.w, h = a.h, lw = a.lw;
-  const int tx = TX ? TX : a.tx, ty = TY ? TY : a.ty;
+  const int tx = TX ? TX : a.taps.tx, ty = TY ? TY : a.taps.ty;
   LavishScaleJob jb{};
   if (job < a.njobs) jb = a.jobs[job];
   const int xs = jb.x_step_qn, ys = jb.y_step_qn, spx = jb.subpel_x_qn, spy = jb.subpel_y_qn;
@@ -140,7 +138,7 @@ __global__ __launch_bounds__(256) void scale_kernel(ScaleArgs a) {
       } else {
         for (int k = 0; k < tx; ++k) s += f[k] * (int)p[k];
       }
-      im[e] = (int16_t)((s + ((1 << a.r0) >> 1)) >> a.r0);
+      im[e] = (int16_t)((s + ((1 << a.rnd.r0) >> 1)) >> a.rnd.r0);
     }
   }
   __syncthreads();
@@ -154,28 +152,25 @@ __global__ __launch_bounds__(256) void scale_kernel(ScaleArgs a) {
     const int y_qn = spy + y * ys;
     const int16_t* f = fys + ((y_qn & ((1 << kScaleBits) - 1)) >> kScaleExtra) * kFRow;
     const int16_t* col = im + ((y_qn >> kScaleBits) << lw) + x;
-    int32_t s = 1 << a.offset_bits;
+    int32_t s = 1 << a.rnd.offset_bits;
     if constexpr (TY != 0) {
 #pragma unroll
       for (int k = 0; k < TY; ++k) s += f[k] * (int)col[k << lw];
     } else {
       for (int k = 0; k < ty; ++k) s += f[k] * (int)col[k << lw];
     }
-    const int32_t res = (uint16_t)((s + ((1 << a.r1) >> 1)) >> a.r1);  // CONV_BUF_TYPE
-    int32_t tmp;
-    if (a.is_compound) {
+    const int32_t res = (uint16_t)((s + ((1 << a.rnd.r1) >> 1)) >> a.rnd.r1);  // CONV_BUF_TYPE
+    int v;
+    if (a.rnd.is_compound) {
       uint16_t* c = conv + (int64_t)y * a.conv_stride + x;
-      if (!a.do_average) {
+      if (!a.rnd.do_average) {
         *c = (uint16_t)res;
         continue;
       }
-      tmp = *c;
-      tmp = a.dist_wtd ? (tmp * a.fwd + res * a.bck) >> 4 : (tmp + res) >> 1;
-      tmp -= a.round_offset;
+      v = conv_average(a.rnd, *c, res);
     } else {
-      tmp = res - a.round_offset;
+      v = (res - a.rnd.round_offset + ((1 << a.rnd.round_bits) >> 1)) >> a.rnd.round_bits;
     }
-    const int v = (tmp + ((1 << a.round_bits) >> 1)) >> a.round_bits;
     dst[(int64_t)y * a.dst_stride + x] = (Pix)min(max(v, 0), pmax);
   }
 }
@@ -183,7 +178,7 @@ __global__ __launch_bounds__(256) void scale_kernel(ScaleArgs a) {
 template <typename Pix>
 void scale_launch(const ScaleArgs& a, int grid, size_t lds, hipStream_t s) {
 #define LAVISH_SCALE_K(X, Y)                                                                   \
-  if (a.tx == X && a.ty == Y) {                                                                \
+  if (a.taps.tx == X && a.taps.ty == Y) {                                                      \
     hipLaunchKernelGGL((scale_kernel<Pix, X, Y>), dim3(grid), dim3(256), lds, s, a);           \
     return;                                                                                    \
   }
@@ -207,15 +202,14 @@ int scale_batch(const void* src, int src_stride, void* dst, int dst_stride, uint
   if (!src || !jobs || !cp || !fpx || !fpy) return -1;
   if ((cp->is_compound && !conv) || ((!cp->is_compound || cp->do_average) && !dst)) return -1;
   if (w < 2 || h < 1 || w > 128 || h > 128 || (w & (w - 1))) return -2;
-  if (highbd ? (bd != 8 && bd != 10 && bd != 12) : bd != 8) return -3;
-  if (fpx->taps < 2 || fpx->taps > kMaxTaps || fpy->taps < 2 || fpy->taps > kMaxTaps ||
-      (fpx->taps & 1) || (fpy->taps & 1) || !fpx->filter_ptr || !fpy->filter_ptr)
-    return -4;
-  const int round_bits = 2 * kFBits - cp->round_0 - cp->round_1;
-  if (cp->round_0 < 0 || cp->round_1 < 0 || round_bits < 0 || cp->round_0 > kFBits ||
-      cp->round_1 > 2 * kFBits)
-    return -5;
+  if (!bd_ok(bd, highbd)) return -3;
   ScaleArgs a{};
+  if (!conv_taps(fpx, fpy, a.taps)) return -4;
+  // (round_1 <= 2 FILTER_BITS, and round_bits >= 0)
+  if (cp->round_0 < 0 || cp->round_1 < 0 || cp->round_0 > kFBits ||
+      cp->round_1 > 2 * kFBits - cp->round_0)
+    return -5;
+  a.rnd = conv_round(*cp, bd);
   a.src = src;
   a.dst = dst;
   a.conv = conv;
@@ -228,27 +222,9 @@ int scale_batch(const void* src, int src_stride, void* dst, int dst_stride, uint
   a.lw = 31 - __builtin_clz(w);
   a.njobs = njobs;
   a.bd = bd;
-  a.tx = fpx->taps;
-  a.ty = fpy->taps;
-  for (int p = 0; p < 16; ++p)  // av1_get_interp_filter_subpel_kernel rows
-    for (int k = 0; k < kMaxTaps; ++k) {
-      a.fx[p][k] = k < a.tx ? fpx->filter_ptr[a.tx * p + k] : 0;
-      a.fy[p][k] = k < a.ty ? fpy->filter_ptr[a.ty * p + k] : 0;
-    }
-  a.r0 = cp->round_0;
-  a.r1 = cp->round_1;
-  a.offset_bits = bd + 2 * kFBits - cp->round_0;
-  a.round_offset =
-      (1 << (a.offset_bits - cp->round_1)) + (1 << (a.offset_bits - cp->round_1 - 1));
-  a.round_bits = round_bits;
-  a.is_compound = cp->is_compound;
-  a.do_average = cp->do_average;
-  a.dist_wtd = cp->use_dist_wtd_comp_avg;
-  a.fwd = cp->fwd_offset;
-  a.bck = cp->bck_offset;
   // the largest intermediate a supported step can make, per block slot
   // (rounded to 8 int16: each slot 16-byte aligned)
-  const int im_rows = (((h - 1) * kMaxStep + (1 << kScaleBits) - 1) >> kScaleBits) + a.ty;
+  const int im_rows = (((h - 1) * kMaxStep + (1 << kScaleBits) - 1) >> kScaleBits) + a.taps.ty;
   a.im_cap = (im_rows * w + 7) & ~7;
   // a power of two, so that 256 / nb threads per slot leaves no thread over
   // (h need not be a power of two: 8x3 would give 10 slots of 25 threads and
@@ -300,41 +276,31 @@ void scale_shim(const Pix* src, int ss, Pix* dst, int ds, int w, int h,
   const int fo_x = fpx->taps / 2 - 1, fo_y = fpy->taps / 2 - 1;
   const int wx = (((w - 1) * xs + spx) >> kScaleBits) + fpx->taps;
   const int wy = (((h - 1) * ys + spy) >> kScaleBits) + fpy->taps;
-  const hipStream_t s = shim_stream();
-  const size_t sb = ((size_t)wx * wy * sizeof(Pix) + 255) & ~(size_t)255;
-  const size_t db = ((size_t)w * h * sizeof(Pix) + 255) & ~(size_t)255;
-  const size_t cb = ((size_t)w * h * 2 + 255) & ~(size_t)255;
-  char* base = (char*)shim_scratch(sb + db + cb + 256);
-  Pix* dsrc = (Pix*)base;
-  Pix* ddst = (Pix*)(base + sb);
-  uint16_t* dconv = (uint16_t*)(base + sb + db);
-  LavishScaleJob* djob = (LavishScaleJob*)(base + sb + db + cb);
-  LAVISH_CHECK(hipMemcpy2DAsync(dsrc, (size_t)wx * sizeof(Pix), src - (int64_t)fo_y * ss - fo_x,
-                                (size_t)ss * sizeof(Pix), (size_t)wx * sizeof(Pix), wy,
-                                hipMemcpyHostToDevice, s));
-  if (cp->is_compound && cp->do_average)
-    LAVISH_CHECK(hipMemcpy2DAsync(dconv, (size_t)w * 2, cp->dst, (size_t)cp->dst_stride * 2,
-                                  (size_t)w * 2, h, hipMemcpyHostToDevice, s));
+  const size_t n = (size_t)w * h;
+  Stage st(Stage::pad((size_t)wx * wy * sizeof(Pix)) + Stage::pad(n * sizeof(Pix)) +
+           Stage::pad(n * sizeof(uint16_t)) + Stage::pad(sizeof(LavishScaleJob)));
+  const Pix* dsrc = st.block(src - (int64_t)fo_y * ss - fo_x, ss, wx, wy);
+  Pix* ddst = st.take_n<Pix>(n);
+  uint16_t* dconv = cp->is_compound && cp->do_average ? st.block(cp->dst, cp->dst_stride, w, h)
+                                                      : st.take_n<uint16_t>(n);
   LavishScaleJob jb{};
   jb.src_off = (int64_t)fo_y * wx + fo_x;
   jb.subpel_x_qn = spx;
   jb.x_step_qn = xs;
   jb.subpel_y_qn = spy;
   jb.y_step_qn = ys;
-  LAVISH_CHECK(hipMemcpyAsync(djob, &jb, sizeof(jb), hipMemcpyHostToDevice, s));
+  const LavishScaleJob* djob = st.copy_in(&jb, 1);
   const int rc = scale_batch(dsrc, wx, ddst, w, dconv, w, w, h, djob, 1, fpx, fpy, cp, bd,
-                             sizeof(Pix) == 2, s);
+                             sizeof(Pix) == 2, st.s);
   if (rc != 0) {
     shim_reject("av1_convolve_2d_scale_hip", rc);
     return;
   }
   if (cp->is_compound && !cp->do_average)
-    LAVISH_CHECK(hipMemcpy2DAsync(cp->dst, (size_t)cp->dst_stride * 2, dconv, (size_t)w * 2,
-                                  (size_t)w * 2, h, hipMemcpyDeviceToHost, s));
+    st.block_out(cp->dst, cp->dst_stride, dconv, w, h);
   else
-    LAVISH_CHECK(hipMemcpy2DAsync(dst, (size_t)ds * sizeof(Pix), ddst, (size_t)w * sizeof(Pix),
-                                  (size_t)w * sizeof(Pix), h, hipMemcpyDeviceToHost, s));
-  LAVISH_CHECK(hipStreamSynchronize(s));
+    st.block_out(dst, ds, ddst, w, h);
+  st.sync();
 }
 }  // namespace
 

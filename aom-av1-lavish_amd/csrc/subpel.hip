@@ -405,9 +405,7 @@ __global__ __launch_bounds__(256) void subpel_kernel(const uint8_t* __restrict__
                                                      const int32_t* __restrict__ cost_lists,
                                                      LavishSubpelResult* out) {
   using S = Sp<W, H>;
-  // XCD-aware: consecutive job quads share an XCD's L2
-  const int nwg = gridDim.x;  // multiple of 8
-  const int wg = (blockIdx.x & 7) * (nwg >> 3) + (blockIdx.x >> 3);
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int lane = threadIdx.x & 63;
   const int j = wg * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (j >= njobs) return;
@@ -523,8 +521,7 @@ void launch(const uint8_t* src, int ss, const uint8_t* ref, int rs, const Lavish
             int njobs, const LavishDiamondResult* fp, int method, int up_kind, int forced_stop,
             int allow_hp, int iters, const LavishMvCostParams& cost, const int32_t* cost_lists,
             LavishSubpelResult* out, hipStream_t s) {
-  int nwg = (njobs + 3) / 4;
-  nwg = (nwg + 7) & ~7;
+  const int nwg = xcd_grid((njobs + 3) / 4);
   hipLaunchKernelGGL((subpel_kernel<W, H>), dim3(nwg), dim3(256), 0, s, src, ss, ref, rs,
                      (const SJob*)jobs, njobs, fp, method, up_kind, forced_stop, allow_hp, iters,
                      cost, cost_lists, out);

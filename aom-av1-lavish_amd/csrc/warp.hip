@@ -21,7 +21,8 @@
 // The filter table (193 x 8 taps) is staged in LDS once per 4 jobs.
 #include <algorithm>
 
-#include "lavish_internal.h"
+#include "conv_dev.h"
+#include "shim_stage.h"
 #include "warp_tables.h"
 
 namespace lavish {
@@ -31,7 +32,6 @@ constexpr int kWmBits = 16;    // WARPEDMODEL_PREC_BITS (mv.h:96)
 constexpr int kWdBits = 10;    // WARPEDDIFF_PREC_BITS
 constexpr int kWpShifts = 64;  // WARPEDPIXEL_PREC_SHIFTS
 constexpr int kWrBits = 6;     // WARP_PARAM_REDUCE_BITS
-constexpr int kFBits = 7;      // FILTER_BITS
 
 struct WarpArgs {
   const void* ref;
@@ -39,8 +39,8 @@ struct WarpArgs {
   uint16_t* dst;
   const LavishWarpJob* jobs;
   int width, height, stride, p_stride, dst_stride, njobs, ss_x, ss_y, bd;
-  int rh, rv, off_h, off_v, round_bits, off_sub;  // derived rounding (per call)
-  int is_compound, do_average, dist_wtd, fwd, bck;
+  int rh, rv, off_h, off_v;  // the two passes' rounding (per call)
+  ConvRound rnd;             // the compound finish
 };
 
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -102,8 +102,7 @@ __global__ __launch_bounds__(64 * kJobsPerWg) void warp_kernel(WarpArgs a) {
   for (int i = threadIdx.x; i < 193 * 8 / 2; i += 64 * kJobsPerWg)
     ((uint32_t*)filt)[i] = ((const uint32_t*)&kWarpedFilter[0][0])[i];
   __syncthreads();
-  const int nwg = gridDim.x;  // multiple of 8: consecutive jobs share an XCD's L2
-  const int wg = (blockIdx.x & 7) * (nwg >> 3) + (blockIdx.x >> 3);
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int j = wg * kJobsPerWg + wave;
@@ -170,16 +169,13 @@ __global__ __launch_bounds__(64 * kJobsPerWg) void warp_kernel(WarpArgs a) {
       const int py = i - p_row + r, px = jc - p_col + c;
       bool write = true;
       int out = 0;
-      if (a.is_compound) {
+      if (a.rnd.is_compound) {
         uint16_t* d = dst + (int64_t)py * a.dst_stride + px;
-        if (!a.do_average) {
+        if (!a.rnd.do_average) {
           *d = (uint16_t)s;
           write = false;
         } else {
-          int32_t tt = *d;
-          tt = a.dist_wtd ? (tt * a.fwd + s * a.bck) >> 4 : (tt + s) >> 1;  // DIST_PRECISION_BITS
-          tt -= a.off_sub;
-          out = (tt + ((1 << a.round_bits) >> 1)) >> a.round_bits;
+          out = conv_average(a.rnd, *d, s);
         }
       } else {
         out = s - (1 << (a.bd - 1)) - (1 << a.bd);
@@ -199,14 +195,7 @@ static void derive(WarpArgs& a, const LavishConvolveParams& cp, int bd, int high
   a.rv = cp.is_compound ? cp.round_1 : 2 * kFBits - a.rh;
   a.off_h = bd + kFBits - 1;
   a.off_v = bd + 2 * kFBits - a.rh;
-  a.round_bits = 2 * kFBits - cp.round_0 - cp.round_1;
-  const int off_bits = bd + 2 * kFBits - cp.round_0;
-  a.off_sub = (1 << (off_bits - cp.round_1)) + (1 << (off_bits - cp.round_1 - 1));
-  a.is_compound = cp.is_compound;
-  a.do_average = cp.do_average;
-  a.dist_wtd = cp.use_dist_wtd_comp_avg;
-  a.fwd = cp.fwd_offset;
-  a.bck = cp.bck_offset;
+  a.rnd = conv_round(cp, bd);
 }
 
 int warp_batch(const void* ref, int width, int height, int stride, void* pred, int p_stride,
@@ -217,7 +206,7 @@ int warp_batch(const void* ref, int width, int height, int stride, void* pred, i
   if (ref == nullptr || pred == nullptr || jobs == nullptr || cp == nullptr) return -1;
   if (width <= 0 || height <= 0 || stride <= 0) return -2;
   if (ss_x < 0 || ss_x > 1 || ss_y < 0 || ss_y > 1) return -3;
-  if (highbd ? (bd != 8 && bd != 10 && bd != 12) : bd != 8) return -4;
+  if (!bd_ok(bd, highbd)) return -4;
   if (cp->is_compound && conv_dst == nullptr) return -5;
   if (cp->do_average && !cp->is_compound) return -5;
   if (cp->round_0 < 0 || cp->round_0 > 8 || cp->round_1 < 0 || cp->round_1 > 14) return -6;
@@ -236,8 +225,7 @@ int warp_batch(const void* ref, int width, int height, int stride, void* pred, i
   a.ss_y = ss_y;
   a.bd = bd;
   derive(a, *cp, bd, highbd);
-  int nwg = (njobs + kJobsPerWg - 1) / kJobsPerWg;
-  nwg = (nwg + 7) & ~7;
+  const int nwg = xcd_grid((njobs + kJobsPerWg - 1) / kJobsPerWg);
   if (highbd)
     hipLaunchKernelGGL(warp_kernel<uint16_t>, dim3(nwg), dim3(64 * kJobsPerWg), 0, s, a);
   else
@@ -322,24 +310,13 @@ static void warp_shim(const int32_t* mat, const Pix* ref, int width, int height,
   x0 = std::min(x0, width - 1); x1 = std::max(x1, 0);
   y0 = std::min(y0, height - 1); y1 = std::max(y1, 0);
   const int ww = x1 - x0 + 1, wh = y1 - y0 + 1;
-  const hipStream_t s = shim_stream();
-  const size_t rb = ((size_t)ww * wh * sizeof(Pix) + 255) & ~(size_t)255;
-  const size_t pb = ((size_t)p_width * p_height * sizeof(Pix) + 255) & ~(size_t)255;
-  const size_t db = ((size_t)p_width * p_height * sizeof(uint16_t) + 255) & ~(size_t)255;
-  char* base = (char*)shim_scratch(rb + pb + db + 256);
-  Pix* dref = (Pix*)base;
-  Pix* dpred = (Pix*)(base + rb);
-  uint16_t* ddst = (uint16_t*)(base + rb + pb);
-  LavishWarpJob* djob = (LavishWarpJob*)(base + rb + pb + db);
-  LAVISH_CHECK(hipMemcpy2DAsync(dref, (size_t)ww * sizeof(Pix), ref + (int64_t)y0 * stride + x0,
-                                (size_t)stride * sizeof(Pix), (size_t)ww * sizeof(Pix), wh,
-                                hipMemcpyHostToDevice, s));
-  LAVISH_CHECK(hipMemcpy2DAsync(dpred, (size_t)p_width * sizeof(Pix), pred,
-                                (size_t)p_stride * sizeof(Pix), (size_t)p_width * sizeof(Pix),
-                                p_height, hipMemcpyHostToDevice, s));
-  if (cp->is_compound)
-    LAVISH_CHECK(hipMemcpy2DAsync(ddst, (size_t)p_width * 2, cp->dst, (size_t)cp->dst_stride * 2,
-                                  (size_t)p_width * 2, p_height, hipMemcpyHostToDevice, s));
+  const size_t n = (size_t)p_width * p_height;
+  Stage st(Stage::pad((size_t)ww * wh * sizeof(Pix)) + Stage::pad(n * sizeof(Pix)) +
+           Stage::pad(n * sizeof(uint16_t)) + Stage::pad(sizeof(LavishWarpJob)));
+  const Pix* dref = st.block(ref + (int64_t)y0 * stride + x0, stride, ww, wh);
+  Pix* dpred = st.block(pred, p_stride, p_width, p_height);
+  uint16_t* ddst = cp->is_compound ? st.block(cp->dst, cp->dst_stride, p_width, p_height)
+                                   : st.take_n<uint16_t>(n);
   LavishWarpJob jb{};
   for (int k = 0; k < 6; ++k) jb.mat[k] = mat[k];
   jb.alpha = alpha;
@@ -351,20 +328,16 @@ static void warp_shim(const int32_t* mat, const Pix* ref, int width, int height,
   jb.p_width = p_width;
   jb.p_height = p_height;
   jb.ref_off = -((int64_t)y0 * ww + x0);  // plane coordinates into the staged window
-  LAVISH_CHECK(hipMemcpyAsync(djob, &jb, sizeof(jb), hipMemcpyHostToDevice, s));
+  const LavishWarpJob* djob = st.copy_in(&jb, 1);
   const int rc = warp_batch(dref, width, height, ww, dpred, p_width, ddst, p_width, djob, 1, ss_x,
-                            ss_y, bd, sizeof(Pix) == 2, cp, s);
+                            ss_y, bd, sizeof(Pix) == 2, cp, st.s);
   if (rc != 0) {
     shim_reject("av1_warp_affine_hip", rc);
     return;
   }
-  LAVISH_CHECK(hipMemcpy2DAsync(pred, (size_t)p_stride * sizeof(Pix), dpred,
-                                (size_t)p_width * sizeof(Pix), (size_t)p_width * sizeof(Pix),
-                                p_height, hipMemcpyDeviceToHost, s));
-  if (cp->is_compound)
-    LAVISH_CHECK(hipMemcpy2DAsync(cp->dst, (size_t)cp->dst_stride * 2, ddst, (size_t)p_width * 2,
-                                  (size_t)p_width * 2, p_height, hipMemcpyDeviceToHost, s));
-  LAVISH_CHECK(hipStreamSynchronize(s));
+  st.block_out(pred, p_stride, dpred, p_width, p_height);
+  if (cp->is_compound) st.block_out(cp->dst, cp->dst_stride, ddst, p_width, p_height);
+  st.sync();
 }
 
 extern "C" void av1_warp_affine_hip(const int32_t* mat, const uint8_t* ref, int width, int height,

@@ -12,6 +12,7 @@
 // blocks.  The lossless path is rare (segments with qindex 0); what matters is
 // that an RTCD-bound encoder never aborts on it.
 #include "lavish_internal.h"
+#include "shim_stage.h"
 
 namespace lavish {
 namespace {
@@ -157,8 +158,7 @@ int lavish_fwht4x4_batch(const int16_t* src_diff, int stride, const LavishPixJob
 int lavish_iwht4x4_add_batch(const int32_t* dqcoeff, const LavishInvJob* jobs, int njobs,
                              void* dst, int dst_stride, int bit_depth, int highbd, void* stream) {
   if (njobs <= 0) return 0;
-  if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) return -3;
-  if (!highbd && bit_depth != 8) return -3;
+  if (!bd_ok(bit_depth, highbd)) return -3;
   const int maxv = (1 << bit_depth) - 1;
   hipStream_t s = (hipStream_t)stream;
   if (highbd)
@@ -173,37 +173,28 @@ int lavish_iwht4x4_add_batch(const int32_t* dqcoeff, const LavishInvJob* jobs, i
 
 // ---- per-call shims (host buffers) ----
 void av1_fwht4x4_hip(const int16_t* input, int32_t* output, int stride) {
-  hipStream_t s = shim_stream();
-  char* base = (char*)shim_scratch(4096);
-  int16_t* din = (int16_t*)base;
-  LavishPixJob* dj = (LavishPixJob*)(base + 256);
-  int32_t* dout = (int32_t*)(base + 512);
+  Stage st(Stage::pad(16 * sizeof(int16_t)) + Stage::pad(sizeof(LavishPixJob)) +
+           Stage::pad(16 * sizeof(int32_t)));
+  const int16_t* din = st.block(input, stride, 4, 4);
   LavishPixJob jb{};
-  LAVISH_CHECK(hipMemcpy2DAsync(din, 4 * sizeof(int16_t), input, (size_t)stride * sizeof(int16_t),
-                                4 * sizeof(int16_t), 4, hipMemcpyHostToDevice, s));
-  LAVISH_CHECK(hipMemcpyAsync(dj, &jb, sizeof(jb), hipMemcpyHostToDevice, s));
-  lavish_fwht4x4_batch(din, 4, dj, 1, dout, s);
-  LAVISH_CHECK(hipMemcpyAsync(output, dout, 16 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-  LAVISH_CHECK(hipStreamSynchronize(s));
+  const LavishPixJob* dj = st.copy_in(&jb, 1);
+  int32_t* dout = st.take_n<int32_t>(16);
+  lavish_fwht4x4_batch(din, 4, dj, 1, dout, st.s);
+  st.copy_out(output, dout, 16);
+  st.sync();
 }
 
 static void iwht_shim(const int32_t* input, uint16_t* dest, int stride, int eob, int bd) {
-  hipStream_t s = shim_stream();
-  char* base = (char*)shim_scratch(4096);
-  int32_t* din = (int32_t*)base;
-  LavishInvJob* dj = (LavishInvJob*)(base + 256);
-  uint16_t* dd = (uint16_t*)(base + 512);
+  Stage st(Stage::pad(16 * sizeof(int32_t)) + Stage::pad(sizeof(LavishInvJob)) +
+           Stage::pad(16 * sizeof(uint16_t)));
+  const int32_t* din = st.copy_in(input, 16);
   LavishInvJob jb{};
   jb.eob = eob;
-  LAVISH_CHECK(hipMemcpyAsync(din, input, 16 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  LAVISH_CHECK(hipMemcpyAsync(dj, &jb, sizeof(jb), hipMemcpyHostToDevice, s));
-  LAVISH_CHECK(hipMemcpy2DAsync(dd, 4 * sizeof(uint16_t), dest, (size_t)stride * sizeof(uint16_t),
-                                4 * sizeof(uint16_t), 4, hipMemcpyHostToDevice, s));
-  const int rc = lavish_iwht4x4_add_batch(din, dj, 1, dd, 4, bd, 1, s);
-  if (rc) shim_reject("lavish_iwht4x4_add_batch", rc);
-  LAVISH_CHECK(hipMemcpy2DAsync(dest, (size_t)stride * sizeof(uint16_t), dd, 4 * sizeof(uint16_t),
-                                4 * sizeof(uint16_t), 4, hipMemcpyDeviceToHost, s));
-  LAVISH_CHECK(hipStreamSynchronize(s));
+  const LavishInvJob* dj = st.copy_in(&jb, 1);
+  uint16_t* dd = st.block(dest, stride, 4, 4);
+  must(lavish_iwht4x4_add_batch(din, dj, 1, dd, 4, bd, 1, st.s), "lavish_iwht4x4_add_batch");
+  st.block_out(dest, stride, dd, 4, 4);
+  st.sync();
 }
 
 // av1/common/av1_rtcd_defs.pl:217-219 (tagged u16 destinations)
