@@ -2,8 +2,10 @@
 // (full_pixel_diamond / diamond_search_sad, av1/encoder/mcomp.c:1318-1526,
 // with the quality recheck :1840-1867) over 16x16 blocks and tiled
 // references with eight jobs per wave, its capped and queue-fed launches, the
-// fused C2 + C3 launch (lavish_txq_frame_search; the only unit that includes
-// txq_dev.h) and the tiled reference copy (lavish_ref_tiles_build).
+// 64-VGPR lean variant that runs beside C2 (diamond_lj_lean_kernel and its
+// redo launch), the fused C2 + C3 launch (lavish_txq_frame_search; the only
+// unit that includes txq_dev.h) and the tiled reference copy
+// (lavish_ref_tiles_build).
 #include <atomic>
 
 #include "mcomp_dev.h"
@@ -352,12 +354,13 @@ __device__ void lj_pass(const Ctx& c, const LjSrc& s, int l, __amdgpu_buffer_rsr
   }
 }
 
+template <bool LIST = false>
 __device__ __forceinline__ void lj_jobs(
     const uint8_t* __restrict__ src, int ss, const uint8_t* __restrict__ ref, int rs,
     const LavishRefTiles& tiles, const Job* __restrict__ jobs, int njobs, int step_param,
     const LavishMvCostParams& cost, const int32_t* dec, int skip,
     LavishDiamondResult* __restrict__ out, int32_t* __restrict__ cost_lists, int j0,
-    uint32_t* res);
+    uint32_t* res, const int* __restrict__ list = nullptr, int nlist = 0);
 
 // one group of WPG x 8 jobs: virtual workgroup vwg of nvwg (a multiple of 8)
 template <int WPG>
@@ -377,17 +380,21 @@ __device__ __forceinline__ void lj_group(
 }
 
 // the eight jobs j0 .. j0 + 7 of one wave (res: this lane group's LDS slot
-// for the runs' results)
+// for the runs' results); LIST: the jobs list[j0 .. j0 + 7] of a list of
+// nlist job indices (the lean search's redo list)
+template <bool LIST>
 __device__ __forceinline__ void lj_jobs(
     const uint8_t* __restrict__ src, int ss, const uint8_t* __restrict__ ref, int rs,
     const LavishRefTiles& tiles, const Job* __restrict__ jobs, int njobs, int step_param,
     const LavishMvCostParams& cost, const int32_t* dec, int skip,
     LavishDiamondResult* __restrict__ out, int32_t* __restrict__ cost_lists, int j0,
-    uint32_t* res) {
+    uint32_t* res, const int* __restrict__ list, int nlist) {
   const int lane = threadIdx.x & 63;
   const int jg = lane >> 3, l = lane & 7;
-  const int j = min(j0 + jg, njobs - 1);  // a surplus group repeats the last job, never stores
-  const bool mine_job = j0 + jg < njobs;
+  const int cnt = LIST ? nlist : njobs;
+  const int jj = min(j0 + jg, cnt - 1);  // a surplus group repeats the last job, never stores
+  const int j = LIST ? list[jj] : jj;
+  const bool mine_job = j0 + jg < cnt;
   const Job jb = jobs[j];
   Ctx c;
   c.src = src + jb.src_off;
@@ -530,8 +537,425 @@ __global__ __launch_bounds__(64 * WPG, LAVISH_LJ_WAVES) void diamond_lj_dyn_kern
   }
 }
 
+// the queue block: the 8 labels' counters, then the lean search's redo
+// counter; the redo list (job indices) follows the block
+constexpr int kLjQueueInts = 9 * kLjQueueStride;
+
 __global__ void lj_queue_zero(int* __restrict__ queue) {
-  if (threadIdx.x < 8 * kLjQueueStride) queue[threadIdx.x] = 0;
+  if (threadIdx.x < kLjQueueInts) queue[threadIdx.x] = 0;
+}
+
+// ---------------------------------------------------------------------------
+// The lean variant of the queue-fed search: the same walk in at most 64 VGPRs
+// and under 3 KB of LDS per workgroup, so a search wave finds a slot on a
+// SIMD whose four transform (C2) workgroups hold 448 of its 512 VGPRs.
+//  - Only the row-skipping pass and its quality check run here.  A job that
+//    fails the check is appended to a redo list (a device counter + job
+//    indices behind the queue's counters) and diamond_lj_redo_kernel, the
+//    next launch on the stream, reruns it from its start with the full body
+//    (lj_jobs<true>, skip = 1): the accumulated steps / searches, the record
+//    and the cost list are diamond_lj_dyn_kernel's.
+//  - Per-job constants (the mv window, the reference mv, the block's origin
+//    in the tiled copy, the clamped start and its cost, the source offset)
+//    sit in a 10-word LDS record per lane group, written once per unit and
+//    read where used; launch-uniform values stay scalar.
+//  - Only source row 2l (sk) is live during the walk; rows l and l + 8 are
+//    reloaded for the variance costs and the quality check.
+//  - A step's 8 candidate loads go in two halves of 4; every offset is a row
+//    part + a column part (tile_off splits that way at any radius).
+//  - The variance costs of a job's runs are evaluated kVarBatch at a time,
+//    their loads in flight together, as byte dot products.
+// The compiler's register count after each of these: DESIGN.md section 4.
+constexpr int kLjRecWords = 10;
+constexpr int kVarBatch = 2;  // results' variance costs in flight together
+enum {
+  kRecRows = 0,   // row_min | row_max << 16
+  kRecCols = 1,   // col_min | col_max << 16
+  kRecFref = 2,   // full_ref_row | full_ref_col << 16
+  kRecRefMv = 3,  // ref_mv_row | ref_mv_col << 16
+  kRecOy = 4,
+  kRecOx = 5,
+  kRecStart = 6,  // the clamped start: row | col << 16
+  kRecC0 = 7,     // its cost
+  kRecSrc = 8     // src_off (2 words)
+};
+__device__ __forceinline__ int lo16(uint32_t v) { return (int)(int16_t)(v & 0xFFFF); }
+__device__ __forceinline__ int hi16(uint32_t v) { return (int)v >> 16; }
+__device__ __forceinline__ uint32_t pack16(int lo, int hi) {
+  return ((uint32_t)hi << 16) | (uint32_t)(uint16_t)lo;
+}
+__device__ __forceinline__ int64_t rec_i64(lds_u32 rec, int at) {
+  return (int64_t)(((uint64_t)rec[at + 1] << 32) | rec[at]);
+}
+
+// mvsad_rate_dec's loads at unsigned indices (in range by the same contract):
+// a scalar table base + a 32-bit lane offset, no 64-bit lane address; no
+// decimated tables (dec null: not the entropy cost) = no loads, the rates
+// are not used
+__device__ __forceinline__ MvRate lean_rate(const int32_t* mvjcost, const int32_t* dec, int kr,
+                                            int kc) {
+  const uint32_t joint = (uint32_t)((kc != 0) | ((kr != 0) << 1));  // av1_get_mv_joint
+  typedef const __attribute__((address_space(1))) int32_t* gi32;
+  return MvRate{((gi32)mvjcost)[joint], ((gi32)dec)[(uint32_t)(kr + kMvDecHalf)],
+                ((gi32)dec)[(uint32_t)(kc + kMvDecHalf + kMvDecN)]};
+}
+// a lane value the compiler may not carry across this point: what depends on
+// it is computed where it is used (carried, the per-lane row offsets, site
+// moves and lane masks hold registers for the whole kernel)
+__device__ __forceinline__ int lane_fresh(int v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+// u: the launch-uniform fields of Ctx (the per-job fields are filled from the
+// record where a helper needs them)
+__device__ __forceinline__ void lj_lean_jobs(
+    const Ctx& u, const uint8_t* __restrict__ src, const uint8_t* __restrict__ ref,
+    __amdgpu_buffer_rsrc_t trs, int oob, const Job* __restrict__ jobs, int njobs, int step_param,
+    const int32_t* dec, LavishDiamondResult* __restrict__ out, int32_t* __restrict__ cost_lists,
+    int j0, lds_u32 res_s, lds_u32 rec_s, int* __restrict__ redo) {
+  // this lane group's slot for the runs' results and its record
+  const int tid = lane_fresh((int)threadIdx.x);
+  const lds_u32 res = res_s + (tid >> 3) * kMaxSteps, rec = rec_s + (tid >> 3) * kLjRecWords;
+  const int jg = (tid & 63) >> 3;
+  int l = tid & 7;
+  const int j = min(j0 + jg, njobs - 1);  // a surplus group repeats the last job, never stores
+  uint32_t sk[4];
+  {
+    const Job jb = jobs[j];
+    const int oy = (int)(jb.ref_off / u.rs), ox = (int)(jb.ref_off - (int64_t)oy * u.rs);
+    const int srow = min(max((int)jb.start_row, (int)jb.row_min), (int)jb.row_max);
+    const int scol = min(max((int)jb.start_col, (int)jb.col_min), (int)jb.col_max);
+    Ctx c = u;
+    c.full_ref_row = rawpel(jb.ref_mv_row);
+    c.full_ref_col = rawpel(jb.ref_mv_col);
+    c.oy = oy;
+    c.ox = ox;
+    load_row<4>(src + jb.src_off + (int64_t)(2 * l) * u.ss, sk);
+    // the start: its SAD once per job (every run restarts there)
+    MvRate m0 = {0, 0, 0};
+    if (dec != nullptr)
+      m0 = lean_rate(u.mvjcost, dec, srow - c.full_ref_row, scol - c.full_ref_col);
+    const u32x4 t = __builtin_amdgcn_raw_buffer_load_b128(
+        trs, (int)tile_off(c, oy + srow + 2 * l, ox + scol), 0, 0);
+    uint32_t acc = sad4(sk[0], t.x, 0);
+    acc = sad4(sk[1], t.y, acc);
+    acc = sad4(sk[2], t.z, acc);
+    acc = sad4(sk[3], t.w, acc);
+    const uint32_t c0 = 2 * group_sum8(acc) + mvsad_finish(c, m0, srow, scol);
+    if (l == 0) {
+      rec[kRecRows] = pack16(jb.row_min, jb.row_max);
+      rec[kRecCols] = pack16(jb.col_min, jb.col_max);
+      rec[kRecFref] = pack16(c.full_ref_row, c.full_ref_col);
+      rec[kRecRefMv] = pack16(jb.ref_mv_row, jb.ref_mv_col);
+      rec[kRecOy] = (uint32_t)oy;
+      rec[kRecOx] = (uint32_t)ox;
+      rec[kRecStart] = pack16(srow, scol);
+      rec[kRecC0] = c0;
+      rec[kRecSrc] = (uint32_t)jb.src_off;
+      rec[kRecSrc + 1] = (uint32_t)((uint64_t)jb.src_off >> 32);
+    }
+  }
+  wave_sync();
+  const int further = kMaxSteps - 1 - step_param;
+  bool active = true, first = true, offc = false;
+  int n = 0, stp = kMaxSteps - step_param - 1, center = 0, nres = 0, steps = 0;
+  int row = lo16(rec[kRecStart]), col = hi16(rec[kRecStart]);
+  uint32_t best = rec[kRecC0];
+  while (__builtin_amdgcn_ballot_w64(active) != 0) {
+    // (the record's reads stay inside the loop: hoisted, they are the
+    // per-job registers again)
+    asm volatile("" ::: "memory");
+    const int rad = 1 << stp;
+    const uint32_t wr = rec[kRecRows], wc = rec[kRecCols], wf = rec[kRecFref];
+    const int row_min = lo16(wr), row_max = hi16(wr), col_min = lo16(wc), col_max = hi16(wc);
+    Ctx c = u;
+    c.full_ref_row = lo16(wf);
+    c.full_ref_col = hi16(wf);
+    // lane l: site l's cost (its loads in flight with the SAD loads below)
+    const int rl = row + site_dr(l) * rad, cl_ = col + site_dc(l) * rad;
+    const bool vl = cl_ >= col_min && cl_ <= col_max && rl >= row_min && rl <= row_max;
+    MvRate mr = {0, 0, 0};
+    if (dec != nullptr && vl && active)
+      mr = lean_rate(u.mvjcost, dec, rl - c.full_ref_row, cl_ - c.full_ref_col);
+    uint32_t mine = 0;
+    if (active) {
+      // the walk's position is in range, so a site is valid iff its row and
+      // column moves stay inside; an out-of-range site reads the
+      // range-checked offset (no memory request)
+      const bool up = row - rad >= row_min, dn = row + rad <= row_max;
+      const bool lf = col - rad >= col_min, rt = col + rad <= col_max;
+      const int y0 = (int)rec[kRecOy] + row + 2 * l, x0 = (int)rec[kRecOx] + col;
+      // tile_off(y, x) = a row part + a column part
+      auto yo = [&](int y) { return (y & 1) * u.fsz + ((y >> 1) << 5); };
+      const int f32 = u.fh << 5;
+      auto xo = [&](int x) { return __mul24(x >> 4, f32) + (x & 15); };
+      const int ym = yo(y0 - rad), yc = yo(y0), yp = yo(y0 + rad);
+      const int xm = xo(x0 - rad), xc = xo(x0), xp = xo(x0 + rad);
+      uint32_t p[8];
+      // two halves of 4 sites: a half's loads all issued, then its SADs
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        u32x4 t[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int dr = site_dr(4 * h + i), dc = site_dc(4 * h + i);
+          const bool v = (dr < 0 ? up : dr > 0 ? dn : true) && (dc < 0 ? lf : dc > 0 ? rt : true);
+          const int off = (dr < 0 ? ym : dr > 0 ? yp : yc) + (dc < 0 ? xm : dc > 0 ? xp : xc);
+          t[i] = __builtin_amdgcn_raw_buffer_load_b128(trs, v ? off : oob, 0, 0);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          uint32_t acc = sad4(sk[0], t[i].x, 0);
+          acc = sad4(sk[1], t[i].y, acc);
+          acc = sad4(sk[2], t[i].z, acc);
+          p[4 * h + i] = sad4(sk[3], t[i].w, acc);
+        }
+      }
+      mine = 2 * scatter_sum8(p, l);
+    }
+    const uint32_t key =
+        (((mine + mvsad_finish(c, mr, rl, cl_)) << 3) | (uint32_t)l) | (vl ? 0u : ~0u);
+    const uint32_t kmin = group_min8(key);
+    if (active) {
+      ++steps;
+      if (kmin < (best << 3)) {
+        best = kmin >> 3;
+        const int i = (int)(kmin & 7);
+        row += site_dr(i) * rad;
+        col += site_dc(i) * rad;
+        offc = true;
+      }
+      if (!offc) ++center;
+      if (--stp < 0) {  // this diamond_search_sad run is over
+        if (l == 0) res[nres] = pack16(col, row);
+        ++nres;
+        if (first) n = center;  // the first run's num00
+        else if (center) n += center;
+        first = false;
+        if (n < further) {  // the next run, one step shorter
+          ++n;
+          const uint32_t st = rec[kRecStart];
+          row = lo16(st);
+          col = hi16(st);
+          best = rec[kRecC0];
+          stp = kMaxSteps - (step_param + n) - 1;
+          center = 0;
+          offc = false;
+        } else {
+          active = false;
+          stp = 0;  // a finished job keeps stepping in place at radius 1 (masked)
+        }
+      }
+    }
+  }
+  wave_sync();
+  // var costs of the runs' results in order, strict "<" (full_pixel_diamond),
+  // kVarBatch results' rows and mv rates in flight at a time; lane l takes
+  // rows l and l + 8.  The linear reference at 32-bit offsets from its
+  // (scalar) base: the tiled copy spans the same buffer in under 2^31 bytes
+  l = lane_fresh(l);
+  const bool mine_job = j0 + jg < njobs;
+  const uint8_t* sp = src + rec_i64(rec, kRecSrc);
+  uint32_t fr[2][4];
+  load_row<4>(sp + (int64_t)l * u.ss, fr[0]);
+  load_row<4>(sp + (int64_t)(l + 8) * u.ss, fr[1]);
+  const uint32_t lin0 = (uint32_t)(((int)rec[kRecOy] + l) * u.rs + (int)rec[kRecOx]);
+  int sme = 0, br = 0, bc = 0;
+  {
+    // sum (a - b)^2 = sum a^2 + sum b^2 - 2 sum a b, in byte dot products
+    // (exact: each sum < 2^22); the source's parts once per job
+    uint32_t saa = 0, sa = 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        saa = __builtin_amdgcn_udot4(fr[h][i], fr[h][i], saa, false);
+        sa = sad4(fr[h][i], 0, sa);
+      }
+    const bool ent = u.cost_type == 0;
+    const int ref_mv_row = lo16(rec[kRecRefMv]), ref_mv_col = hi16(rec[kRecRefMv]);
+    typedef const __attribute__((address_space(1))) int32_t* gi32;
+    for (int i0 = 0; __builtin_amdgcn_ballot_w64(i0 < nres) != 0; i0 += kVarBatch) {
+      uint32_t t[kVarBatch][2][4];
+      MvRate m[kVarBatch];
+#pragma unroll
+      for (int k = 0; k < kVarBatch; ++k) {
+        const uint32_t q = res[min(i0 + k, nres - 1)];  // (a surplus slot repeats the last)
+        const int r = hi16(q), cc = lo16(q);
+        // mv_rate's loads, branch-free as mvsad_rate's (index 0 of kZeroRate
+        // for the other cost types)
+        const int dr = r * 8 - ref_mv_row, dc = cc * 8 - ref_mv_col;
+        const int joint = ent ? ((dc != 0) | ((dr != 0) << 1)) : 0;
+        m[k] = MvRate{((gi32)u.mvjcost)[joint], ((gi32)u.mvcost0)[ent ? dr : 0],
+                      ((gi32)u.mvcost1)[ent ? dc : 0]};
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+          load_row<4>(ref + (uint32_t)(lin0 + (uint32_t)((r + 8 * h) * u.rs + cc)), t[k][h]);
+      }
+#pragma unroll
+      for (int k = 0; k < kVarBatch; ++k) {
+        const uint32_t q = res[min(i0 + k, nres - 1)];
+        const int r = hi16(q), cc = lo16(q);
+        uint32_t sbb = saa, sab = 0, sb = 0;
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            sbb = __builtin_amdgcn_udot4(t[k][h][i], t[k][h][i], sbb, false);
+            sab = __builtin_amdgcn_udot4(fr[h][i], t[k][h][i], sab, false);
+            sb = sad4(t[k][h][i], 0, sb);
+          }
+        const uint32_t ts = group_sum8(sa - sb), tq = group_sum8(sbb - 2 * sab);
+        const uint32_t var = tq - (uint32_t)(((int64_t)(int)ts * (int)ts) / 256);
+        // mv_err_cost (mv_cost of mcomp_dev.h)
+        const int dr = r * 8 - ref_mv_row, dc = cc * 8 - ref_mv_col;
+        const int mvc =
+            ent ? (int)(((int64_t)(m[k].j + m[k].r + m[k].c) * u.error_per_bit + 8192) >> 14)
+                : (u.sse_lambda * (abs(dr) + abs(dc))) >> 3;
+        const int v = (int)var + mvc;
+        if (i0 + k < nres && (i0 + k == 0 || v < sme)) {
+          sme = v;
+          br = r;
+          bc = cc;
+        }
+      }
+    }
+  }
+  // quality check of the row-skipping search (mcomp.c:1840-1867): sad and
+  // sad_skip at the result, rows l and l + 8 of lane l (same parity as l)
+  bool full;
+  {
+    uint32_t all = 0;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      uint32_t t[4];
+      load_row<4>(ref + (uint32_t)(lin0 + (uint32_t)((br + 8 * k) * u.rs + bc)), t);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) all = sad4(fr[k][i], t[i], all);
+    }
+    const int sad = (int)group_sum8(all);
+    const int ssad = (int)(2 * group_sum8((l & 1) ? 0u : all));
+    full = sad > 16 && abs(ssad - sad) * 10 >= max(sad, 1) * 9;
+  }
+  if (!mine_job) return;
+  if (full) {  // the full-row rerun is diamond_lj_redo_kernel's
+    if (l == 0)
+      redo[kLjQueueStride + __hip_atomic_fetch_add(redo, 1, __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT)] = j;
+    return;
+  }
+  if (l == 0) {
+    LavishDiamondResult r;
+    r.best_row = (int16_t)br;
+    r.best_col = (int16_t)bc;
+    r.bestsme = sme;
+    r.steps = steps;
+    r.searches = nres;
+    out[j] = r;
+  }
+  if (cost_lists != nullptr) {  // calc_int_sad_list around (br, bc): centre, left, bottom, right, top
+    asm volatile("" ::: "memory");  // (the record read here, not carried through the var costs)
+    const uint32_t wr = rec[kRecRows], wc = rec[kRecCols], wf = rec[kRecFref];
+    const int row_min = lo16(wr), row_max = hi16(wr), col_min = lo16(wc), col_max = hi16(wc);
+    Ctx c = u;
+    c.full_ref_row = lo16(wf);
+    c.full_ref_col = hi16(wf);
+    c.oy = (int)rec[kRecOy];
+    c.ox = (int)rec[kRecOx];
+    l = lane_fresh(l);
+    LjSrc s;
+    load_row<4>(sp + (int64_t)(2 * l) * u.ss, s.sk);
+    int rr[5], cc[5];
+    bool vv[5];
+    uint32_t sd[5];
+#pragma unroll
+    for (int t = 0; t < 5; ++t) {
+      rr[t] = br + (t == 2 ? 1 : t == 4 ? -1 : 0);
+      cc[t] = bc + (t == 1 ? -1 : t == 3 ? 1 : 0);
+      vv[t] = t == 0 || (cc[t] >= col_min && cc[t] <= col_max && rr[t] >= row_min && rr[t] <= row_max);
+    }
+    // lane l: point l's mv cost (lanes 5-7 repeat point 4 and store nothing)
+    const int tl = min(l, 4);
+    const int rl = br + (tl == 2 ? 1 : tl == 4 ? -1 : 0), cl_ = bc + (tl == 1 ? -1 : tl == 3 ? 1 : 0);
+    const bool vl =
+        tl == 0 || (cl_ >= col_min && cl_ <= col_max && rl >= row_min && rl <= row_max);
+    MvRate m = {0, 0, 0};
+    if (dec != nullptr)  // (in-range indices)
+      m = lean_rate(u.mvjcost, dec, (vl ? rl : br) - c.full_ref_row,
+                    (vl ? cl_ : bc) - c.full_ref_col);
+    lj_sads<true, 5>(c, s, l, trs, oob, rr, cc, vv, sd);
+    uint32_t sdl = sd[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) sdl = tl == t ? sd[t] : sdl;
+    const int mine = vl ? (int)(sdl + mvsad_finish(c, m, rl, cl_)) : INT_MAX;
+    if (l < 5) cost_lists[5 * (int64_t)j + l] = mine;
+  }
+}
+
+#ifndef LAVISH_LJ_LEAN_WAVES
+#define LAVISH_LJ_LEAN_WAVES 8  // 512 / 8 = 64 VGPRs: the room beside four transform workgroups
+#endif
+template <int WPG>
+__global__ __launch_bounds__(64 * WPG, LAVISH_LJ_LEAN_WAVES) void diamond_lj_lean_kernel(
+    const uint8_t* __restrict__ src, int ss, const uint8_t* __restrict__ ref, int rs,
+    LavishRefTiles tiles, const Job* __restrict__ jobs, int njobs, int step_param,
+    LavishMvCostParams cost, const int32_t* dec, LavishDiamondResult* __restrict__ out,
+    int32_t* __restrict__ cost_lists, int* __restrict__ queue) {
+  __shared__ uint32_t res_s[WPG][kLjJobs][kMaxSteps];
+  __shared__ uint32_t rec_s[WPG][kLjJobs][kLjRecWords];
+  const int units = (njobs + kLjJobs - 1) / kLjJobs;
+  const int x = blockIdx.x & 7;
+  const int u0 = units * x / 8, u1 = units * (x + 1) / 8;
+  const int lane = threadIdx.x & 63;
+  Ctx u{};
+  u.ss = ss;
+  u.rs = rs;
+  u.cost_type = cost.mv_cost_type;
+  u.sad_lambda = sad_lambda(cost.mv_cost_type);
+  u.sse_lambda = sse_lambda(cost.mv_cost_type);
+  u.sad_per_bit = cost.sad_per_bit;
+  u.error_per_bit = cost.error_per_bit;
+  const bool ent = cost.mv_cost_type == 0;
+  u.mvjcost = ent ? cost.mvjcost : kZeroRate;
+  u.mvcost0 = ent ? cost.mvcost[0] : kZeroRate;
+  u.mvcost1 = ent ? cost.mvcost[1] : kZeroRate;
+  u.tiles = tiles.data;
+  u.fh = tiles.field_rows;
+  u.fsz = (int)tiles.field_bytes;
+  const int oob = (int)(2 * tiles.field_bytes);
+  const __amdgpu_buffer_rsrc_t trs =
+      __builtin_amdgcn_make_buffer_rsrc((void*)tiles.data, 0, oob, 0x00020000);
+  int* q = queue + x * kLjQueueStride;
+  for (;;) {
+    int t = 0;
+    if (lane == 0) t = __hip_atomic_fetch_add(q, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    t = __builtin_amdgcn_readfirstlane(t);
+    if (u0 + t >= u1) break;  // every wave of the label ends here once the range is drained
+    lj_lean_jobs(u, src, ref, trs, oob, jobs, njobs, step_param, dec, out, cost_lists,
+                 (u0 + t) * kLjJobs, (lds_u32)&res_s[0][0][0], (lds_u32)&rec_s[0][0][0],
+                 queue + 8 * kLjQueueStride);
+    wave_sync();  // the next unit's record after this unit's last read
+  }
+}
+
+// the lean search's redo list, walked by a fixed grid with the full body
+// (both passes); an empty list ends the kernel at once
+template <int WPG>
+__global__ __launch_bounds__(64 * WPG, LAVISH_LJ_WAVES) void diamond_lj_redo_kernel(
+    const uint8_t* __restrict__ src, int ss, const uint8_t* __restrict__ ref, int rs,
+    LavishRefTiles tiles, const Job* __restrict__ jobs, int njobs, int step_param,
+    LavishMvCostParams cost, const int32_t* dec, LavishDiamondResult* __restrict__ out,
+    int32_t* __restrict__ cost_lists, const int* __restrict__ redo) {
+  __shared__ uint32_t res_s[WPG][kLjJobs][kMaxSteps];
+  const int n = min(redo[0], njobs);
+  if (n <= 0) return;
+  const int units = (n + kLjJobs - 1) / kLjJobs;
+  const int lane = threadIdx.x & 63;
+  const int wave = WPG == 1 ? 0 : threadIdx.x >> 6;
+  for (int v = blockIdx.x * WPG + wave; v < units; v += gridDim.x * WPG)
+    lj_jobs<true>(src, ss, ref, rs, tiles, jobs, njobs, step_param, cost, dec, 1, out, cost_lists,
+                  v * kLjJobs, res_s[wave][lane >> 3], redo + kLjQueueStride, n);
 }
 
 // ---------------------------------------------------------------------------
@@ -586,7 +1010,7 @@ __global__ __launch_bounds__(256) void mvcost_dec_kernel(const int32_t* __restri
                                                          int32_t* __restrict__ dec,
                                                          int* __restrict__ queue) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (queue != nullptr && i < 8 * kLjQueueStride) queue[i] = 0;
+  if (queue != nullptr && i < kLjQueueInts) queue[i] = 0;
   if (i >= 2 * kMvDecN) return;
   const int k = (i % kMvDecN) - kMvDecHalf;
   dec[i] = (i < kMvDecN ? mvcost0 : mvcost1)[8 * k];
@@ -601,6 +1025,11 @@ static int lj_grid_cap() { return g_lj_cap.load(std::memory_order_relaxed); }
 // a capped grid: 1 = units pulled from queues (default), 0 = the static
 // grid-stride (lavish_set_search_schedule, A/B)
 static std::atomic<int> g_lj_queue{1};
+// 0 = auto: the lean kernel for a capped, queue-fed search with the
+// downsampled SAD; 1 = always diamond_lj_kernel / diamond_lj_dyn_kernel;
+// 2 = lean whenever the downsampled SAD is on (lavish_set_search_variant)
+static std::atomic<int> g_lj_variant{0};
+constexpr int kLjRedoGrid = 128;  // workgroups of the lean search's follow-up launch
 
 // LavishRefTiles copy through LDS, both sides coalesced: a workgroup takes
 // field f, strips [k0, k0 + 8) and field rows [fy0, fy0 + 32): it reads the
@@ -659,9 +1088,14 @@ void launch_lj(const uint8_t* src, int ss, const uint8_t* ref, int rs, const Lav
   const int cap = lj_grid_cap();
   const int grid = cap > 0 && cap < nwg ? cap : nwg;
   // a capped grid pulls its units from the queues (diamond_lj_dyn_kernel)
-  const bool dyn = grid < nwg && g_lj_queue.load(std::memory_order_relaxed);
+  const int variant = g_lj_variant.load(std::memory_order_relaxed);
+  const bool queued = grid < nwg && g_lj_queue.load(std::memory_order_relaxed);
+  // the lean kernel is queue-fed at any grid (capless: the queues cover all units)
+  const bool lean = skip != 0 && (variant == 2 || (variant == 0 && queued));
+  const bool dyn = queued || lean;
   constexpr size_t kDecBytes = 2 * kMvDecN * sizeof(int32_t);
-  const size_t qbytes = dyn ? 8 * kLjQueueStride * sizeof(int) : 0;
+  // the queue block, then the lean search's redo list (a job index per job)
+  const size_t qbytes = dyn ? (kLjQueueInts + (lean ? (size_t)njobs : 0)) * sizeof(int) : 0;
   int32_t* dec = nullptr;
   int* queue = nullptr;
   char* scr = nullptr;
@@ -674,9 +1108,17 @@ void launch_lj(const uint8_t* src, int ss, const uint8_t* ref, int rs, const Lav
     hipLaunchKernelGGL(mvcost_dec_kernel, dim3((2 * kMvDecN + 255) / 256), dim3(256), 0,
                        s, cost.mvcost[0], cost.mvcost[1], dec, queue);
   } else if (dyn) {
-    hipLaunchKernelGGL(lj_queue_zero, dim3(1), dim3(8 * kLjQueueStride), 0, s, queue);
+    hipLaunchKernelGGL(lj_queue_zero, dim3(1), dim3(kLjQueueInts), 0, s, queue);
   }
-  if (dyn)
+  if (lean) {
+    hipLaunchKernelGGL(diamond_lj_lean_kernel<wpg>, dim3(grid), dim3(64 * wpg), 0, s, src, ss,
+                       ref, rs, t, (const Job*)jobs, njobs, step_param, cost,
+                       (const int32_t*)dec, out, cost_lists, queue);
+    hipLaunchKernelGGL(diamond_lj_redo_kernel<wpg>, dim3(min(kLjRedoGrid, grid)), dim3(64 * wpg),
+                       0, s, src, ss, ref, rs, t, (const Job*)jobs, njobs, step_param, cost,
+                       (const int32_t*)dec, out, cost_lists,
+                       (const int*)(queue + 8 * kLjQueueStride));
+  } else if (dyn)
     hipLaunchKernelGGL(diamond_lj_dyn_kernel<wpg>, dim3(grid), dim3(64 * wpg), 0, s, src,
                        ss, ref, rs, t, (const Job*)jobs, njobs, step_param, cost,
                        (const int32_t*)dec, skip, out, cost_lists, queue);
@@ -694,6 +1136,12 @@ using namespace lavish;
 extern "C" int lavish_set_search_schedule(int queued) {
   if (queued != 0 && queued != 1) return -1;
   lavish::g_lj_queue.store(queued, std::memory_order_relaxed);
+  return 0;
+}
+
+extern "C" int lavish_set_search_variant(int variant) {
+  if (variant < 0 || variant > 2) return -1;
+  lavish::g_lj_variant.store(variant, std::memory_order_relaxed);
   return 0;
 }
 

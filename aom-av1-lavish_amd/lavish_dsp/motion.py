@@ -97,6 +97,9 @@ if hasattr(_lib, "lavish_set_search_workgroup_cap"):  # (older experiment builds
 if hasattr(_lib, "lavish_set_search_schedule"):
     _lib.lavish_set_search_schedule.argtypes = [_i32]
     _lib.lavish_set_search_schedule.restype = _i32
+if hasattr(_lib, "lavish_set_search_variant"):  # (an A/B against an older build)
+    _lib.lavish_set_search_variant.argtypes = [_i32]
+    _lib.lavish_set_search_variant.restype = _i32
 
 
 class RefTiles:
@@ -165,6 +168,19 @@ def set_search_schedule(queued):
     rc = _lib.lavish_set_search_schedule(1 if queued else 0)
     if rc:
         raise ValueError("lavish_set_search_schedule(%r): %d" % (queued, rc))
+
+
+SEARCH_VARIANT_AUTO, SEARCH_VARIANT_FULL, SEARCH_VARIANT_LEAN = 0, 1, 2
+
+
+def set_search_variant(variant):
+    """lavish_set_search_variant: the kernel of a 16x16 tiled DIAMOND search
+    with the downsampled SAD -- SEARCH_VARIANT_AUTO (lean when capped and
+    queue-fed), _FULL (never lean) or _LEAN (lean at any grid); results do
+    not depend on it."""
+    rc = _lib.lavish_set_search_variant(int(variant))
+    if rc:
+        raise ValueError("lavish_set_search_variant(%r): %d" % (variant, rc))
 
 
 def default_mv_cost_tables(allow_hp=False):

@@ -772,6 +772,16 @@ int lavish_set_search_workgroup_cap(int workgroups);
  * -1 for another value.  No reference counterpart. */
 int lavish_set_search_schedule(int queued);
 
+/* Which kernel runs a 16x16 DIAMOND search over tiled references with
+ * use_downsampled_sad: 0 (default) auto -- the lean kernel (at most 64 VGPRs,
+ * so a search wave fits on a SIMD beside four transform workgroups; jobs
+ * whose downsampled-SAD result fails the quality recheck are rerun by a
+ * follow-up launch on the same stream) when the grid is capped and
+ * queue-fed, the full kernels otherwise; 1 always the full kernels; 2 the
+ * lean kernel at any grid (uncapped: the queues cover every unit).  Results
+ * do not depend on it; -1 for another value.  No reference counterpart. */
+int lavish_set_search_variant(int variant);
+
 /* ---- sub-pixel refinement ------------------------
  * av1_find_best_sub_pixel_tree_pruned_more (av1/encoder/mcomp.c:2907-2981;
  * subpel_search_method SUBPEL_TREE_PRUNED_MORE, speed >= 4) without a cost
