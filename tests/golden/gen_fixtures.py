@@ -651,120 +651,171 @@ def mesh_row(m):
             m.get("fine", 0), m.get("intra", 0)] + [v for ri in pat for v in ri]
 
 
+class FullpelRef:
+    """av1_full_pixel_search (av1/encoder/mcomp.c:1755-1895) executed from the
+    reference on planes of the caller's: the translation unit, the search-site
+    configurations of `methods` at `stride`, the mv cost tables (`tables`:
+    nmv_cost_tables()'s dict; a search takes the low-precision pair unless
+    told otherwise) and the frame geometry the mv limits are taken from."""
+
+    def __init__(self, methods, tables, stride, width, height, border):
+        self.tu = tu = C.TU(REF, ["aom_dsp/sad.c", "aom_dsp/variance.c", "av1/encoder/mcomp.c"],
+                            C.reference_defines(REF))
+        check_errors(tu, ["av1_full_pixel_search", "av1_set_mv_search_range"] +
+                     sorted({MS_INIT[m][0] for m in methods}))
+        self.E = tu.enums
+        self.stride, self.W, self.H, self.BORDER = stride, width, height, border
+        self.cfgs = {}
+        for m in methods:
+            cfg = tu.struct_obj("search_site_config")
+            fname, level = MS_INIT[m]
+            tu.func(fname)(cfg, stride, level)
+            self.cfgs[m] = cfg
+        self.tabs = {}
+        for nm in ("lp", "hp"):
+            mj = tu.buffer("int", tables["mvjcost_" + nm].tolist())
+            mc = [tu.buffer("int", tables["mvcost_" + nm][k].tolist()) for k in range(2)]
+            self.tabs[nm] = (mj, [C.Pointer(c.buf, MV_MAX, c.ty) for c in mc])
+        self.mi_params = tu.struct_obj("CommonModeInfoParams")
+        _set(self.mi_params.buf[0], mi_rows=((height + 7) & ~7) // 4,
+             mi_cols=((width + 7) & ~7) // 4)
+        self.vtabs = {}
+
+    def set_planes(self, src_np, refs_np):
+        self.src_buf = self.tu.buffer("uint8_t", src_np.reshape(-1).tolist())
+        self.ref_bufs = [self.tu.buffer("uint8_t", r.reshape(-1).tolist()) for r in refs_np]
+
+    def vtab(self, bw, bh):
+        if (bw, bh) not in self.vtabs:
+            fn = self.tu.func
+            vtab = self.tu.struct_obj("aom_variance_fn_ptr_t")
+            sz = "%dx%d" % (bw, bh)
+            _set(vtab.buf[0], sdf=fn("aom_sad%s" % sz), sdsf=fn("aom_sad_skip_%s" % sz),
+                 vf=fn("aom_variance%s" % sz), sdx4df=fn("aom_sad%sx4d" % sz),
+                 sdx3df=fn("aom_sad%sx3d" % sz), sdsx4df=fn("aom_sad_skip_%sx4d" % sz))
+            self.vtabs[(bw, bh)] = vtab
+        return self.vtabs[(bw, bh)]
+
+    def limits(self, by, bx, bw, bh, ref_mv):
+        """[col_min, col_max, row_min, row_max] of av1_set_mv_limits followed
+        by av1_set_mv_search_range(ref_mv)."""
+        tu = self.tu
+        lim = tu.struct_obj("FullMvLimits")
+        tu.func("av1_set_mv_limits")(self.mi_params, lim, by // 4, bx // 4, bh // 4, bw // 4,
+                                     self.BORDER)
+        rmv = tu.struct_obj("MV")
+        _set(rmv.buf[0], row=ref_mv[0], col=ref_mv[1])
+        tu.func("av1_set_mv_search_range")(lim, rmv)
+        return [_get(lim.buf[0], f) for f in ("col_min", "col_max", "row_min", "row_max")]
+
+    def search(self, bw, bh, mname, use_cl, ctype, skip, step_param, src_off, k, ref_off, ref_mv,
+               start, lims, epb, spb, mrow=None, mesh_thresh=0, hp=False):
+        """One av1_full_pixel_search: the block at src_off of the source and
+        ref_off of reference plane k, window `lims`; mrow: a mesh_row().
+        Returns (best row, best col, var, the five cost-list entries)."""
+        tu, E, stride = self.tu, self.E, self.stride
+        vtab = self.vtab(bw, bh)
+        sbuf = tu.struct_obj("struct buf_2d")
+        _set(sbuf.buf[0], buf=C.Pointer(self.src_buf.buf, src_off, C.UCHAR),
+             stride=stride, width=bw, height=bh)
+        rbuf = tu.struct_obj("struct buf_2d")
+        _set(rbuf.buf[0], buf=C.Pointer(self.ref_bufs[k].buf, ref_off, C.UCHAR),
+             stride=stride, width=self.W, height=self.H)
+        ms = tu.struct_obj("FULLPEL_MOTION_SEARCH_PARAMS")
+        P = ms.buf[0]
+        bsize = E["BLOCK_%dX%d" % (bw, bh)]
+        if mrow is None:
+            _set(P, bsize=bsize, vfp=vtab, search_method=E[mname],
+                 search_sites=self.cfgs[mname], run_mesh_search=0, prune_mesh_search=0,
+                 mesh_search_mv_diff_threshold=4, force_mesh_thresh=mesh_thresh,
+                 fine_search_interval=0, is_intra_mode=0, fast_obmc_search=0)
+        else:
+            _set(P, bsize=bsize, vfp=vtab, search_method=E[mname],
+                 search_sites=self.cfgs[mname], fast_obmc_search=0,
+                 **dict(zip(MESH_FIELDS[:6], mrow[:6])))
+            pats = tu.buffer("struct MESH_PATTERN", 4)
+            for i in range(4):
+                _set(pats.buf[i], range=mrow[6 + 2 * i], interval=mrow[7 + 2 * i])
+            # (the set the search reads: mesh_patterns[is_intra_mode])
+            _get(P, "mesh_patterns")[0] = pats
+            _get(P, "mesh_patterns")[1] = pats
+        msb = _get(P, "ms_buffers")
+        _set(msb, ref=rbuf, src=sbuf, second_pred=None, mask=None, mask_stride=0,
+             inv_mask=0, wsrc=None, obmc_mask=None)
+        L = tu.struct_obj("FullMvLimits").buf[0]
+        _set(L, col_min=lims[0], col_max=lims[1], row_min=lims[2], row_max=lims[3])
+        _set(P, mv_limits=L)
+        rmv = tu.struct_obj("MV")
+        _set(rmv.buf[0], row=ref_mv[0], col=ref_mv[1])
+        mcp = _get(P, "mv_cost_params")
+        fref = tu.func("get_fullmv_from_mv")(rmv)
+        mj, mc = self.tabs["hp" if hp else "lp"]
+        _set(mcp, ref_mv=rmv, full_ref_mv=fref, mv_cost_type=E[ctype], mvjcost=mj,
+             error_per_bit=epb, sad_per_bit=spb)
+        _get(mcp, "mvcost")[0], _get(mcp, "mvcost")[1] = mc[0], mc[1]
+        pre = "sds" if (skip and bh >= 16) else "sd"
+        vt = vtab.buf[0]
+        _set(P, sdf=_get(vt, "sdsf" if pre == "sds" else "sdf"),
+             sdx4df=_get(vt, "sdsx4df" if pre == "sds" else "sdx4df"),
+             sdx3df=_get(vt, "sdsx4df" if pre == "sds" else "sdx3df"))
+        smv = C.new_obj(tu.ctype("FULLPEL_MV"))
+        _set(smv, row=start[0], col=start[1])
+        best = tu.struct_obj("FULLPEL_MV")
+        cl = tu.buffer("int", [0x7FFFFFFF] * 5) if use_cl else None
+        var = tu.func("av1_full_pixel_search")(smv, ms, step_param, cl, best, None)
+        bm = best.buf[0]
+        return (_get(bm, "row"), _get(bm, "col"), var,
+                list(cl.buf) if use_cl else [0x7FFFFFFF] * 5)
+
+
 def gen_mcomp(blocks=None, cases=None, methods=("DIAMOND", "BIGDIA", "FAST_BIGDIA"),
-              name="fix_mcomp.npz", seed_off=4, mesh_thresh=0):
+              name="fix_mcomp.npz", seed_off=4, mesh_thresh=0, planes=None, lambdas=None):
     """av1_full_pixel_search (av1/encoder/mcomp.c:1755-1895) over the DIAMOND,
     BIGDIA (do_init_search 1) and FAST_BIGDIA (do_init_search 0) methods with
     the entropy / L1 / none mv costs, with and without the downsampled-SAD
     speed feature and a cost list, on a small synthetic frame pair; plus the
     default-context mv cost tables and the mv limits of av1_set_mv_limits /
     av1_set_mv_search_range.  (blocks, cases, methods, name: the same for
-    another method set -- fix_mcomp2.npz.)"""
+    another method set -- fix_mcomp2.npz; planes: (src, refs) padded by 160
+    around a 160x128 frame instead of the synthetic pair; lambdas: b ->
+    (error_per_bit, sad_per_bit) of a block's b-th job.)"""
     blocks = MS_BLOCKS if blocks is None else blocks
     cases = MS_CASES if cases is None else cases
+    lambdas = lambdas or (lambda b: (31 + 7 * (b % 3), 3 + (b % 4)))
     sys.path.insert(0, os.path.join(os.path.dirname(HERE), "..", "aom-av1-lavish_amd"))
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(HERE)), "aom-av1-lavish_amd"))
     import lavish_dsp.synth as synth
     out = nmv_cost_tables()
-    tu = C.TU(REF, ["aom_dsp/sad.c", "aom_dsp/variance.c", "av1/encoder/mcomp.c"],
-              C.reference_defines(REF))
-    check_errors(tu, ["av1_full_pixel_search", "av1_set_mv_search_range"] +
-                 sorted({MS_INIT[m][0] for m in methods}))
-    E = tu.enums
     W, H, BORDER, NREF = 160, 128, 160, 2
-    src_np, refs_np = synth.motion_planes(W, H, NREF, BORDER, seed=4321)
+    src_np, refs_np = planes or synth.motion_planes(W, H, NREF, BORDER, seed=4321)
     stride = src_np.shape[1]
+    R = FullpelRef(methods, out, stride, W, H, BORDER)
+    E = R.E
     out["src"], out["refs"] = src_np, refs_np
     out["geom"] = np.array([W, H, BORDER, NREF], np.int32)
-    src_buf = tu.buffer("uint8_t", src_np.reshape(-1).tolist())
-    ref_bufs = [tu.buffer("uint8_t", r.reshape(-1).tolist()) for r in refs_np]
+    R.set_planes(src_np, refs_np)
     org = BORDER * stride + BORDER
-    cfgs = {}
-    for m in methods:
-        cfg = tu.struct_obj("search_site_config")
-        fname, level = MS_INIT[m]
-        tu.func(fname)(cfg, stride, level)
-        cfgs[m] = cfg
-    mj = tu.buffer("int", out["mvjcost_lp"].tolist())
-    mc = [tu.buffer("int", out["mvcost_lp"][k].tolist()) for k in range(2)]
-    mc = [C.Pointer(c.buf, MV_MAX, c.ty) for c in mc]
-    mi_params = tu.struct_obj("CommonModeInfoParams")
-    _set(mi_params.buf[0], mi_rows=((H + 7) & ~7) // 4, mi_cols=((W + 7) & ~7) // 4)
     rnd = ACMRandom(0xbaba + seed_off)
     jobs = []
     for (bw, bh, nblk) in blocks:
-        fn = tu.func
-        vtab = tu.struct_obj("aom_variance_fn_ptr_t")
         sz = "%dx%d" % (bw, bh)
-        _set(vtab.buf[0], sdf=fn("aom_sad%s" % sz), sdsf=fn("aom_sad_skip_%s" % sz),
-             vf=fn("aom_variance%s" % sz), sdx4df=fn("aom_sad%sx4d" % sz),
-             sdx3df=fn("aom_sad%sx3d" % sz), sdsx4df=fn("aom_sad_skip_%sx4d" % sz))
-        bsize = E["BLOCK_%dX%d" % (bw, bh)]
         for ci, (mname, use_cl, ctype, skip, step_param, *_) in enumerate(cases):
             for b in range(nblk):
                 by = rnd.generate(H // bh) * bh
                 bx = rnd.generate(W // bw) * bw
                 k = rnd.generate(NREF)
                 ref_mv = [(0, 0), (13, -21), (-40, 33), (24, 8), (-3, -77)][rnd.generate(5)]
-                lim = tu.struct_obj("FullMvLimits")
-                tu.func("av1_set_mv_limits")(mi_params, lim, by // 4, bx // 4, bh // 4, bw // 4,
-                                             BORDER)
-                rmv = tu.struct_obj("MV")
-                _set(rmv.buf[0], row=ref_mv[0], col=ref_mv[1])
-                tu.func("av1_set_mv_search_range")(lim, rmv)
-                L = lim.buf[0]
-                lims = [_get(L, f) for f in ("col_min", "col_max", "row_min", "row_max")]
+                lims = R.limits(by, bx, bw, bh, ref_mv)
                 start = ((ref_mv[0] + 4) >> 3, (ref_mv[1] + 4) >> 3) if b % 3 else \
                     (rnd.generate(41) - 20, rnd.generate(41) - 20)
-                # buffers
-                sbuf = tu.struct_obj("struct buf_2d")
-                _set(sbuf.buf[0], buf=C.Pointer(src_buf.buf, org + by * stride + bx, C.UCHAR),
-                     stride=stride, width=bw, height=bh)
-                rbuf = tu.struct_obj("struct buf_2d")
-                _set(rbuf.buf[0], buf=C.Pointer(ref_bufs[k].buf, org + by * stride + bx, C.UCHAR),
-                     stride=stride, width=W, height=H)
-                ms = tu.struct_obj("FULLPEL_MOTION_SEARCH_PARAMS")
-                P = ms.buf[0]
                 mrow = mesh_row(cases[ci][5]) if len(cases[ci]) > 5 else None
-                if mrow is None:
-                    _set(P, bsize=bsize, vfp=vtab, search_method=E[mname],
-                         search_sites=cfgs[mname], run_mesh_search=0, prune_mesh_search=0,
-                         mesh_search_mv_diff_threshold=4, force_mesh_thresh=mesh_thresh,
-                         fine_search_interval=0, is_intra_mode=0, fast_obmc_search=0)
-                else:
-                    _set(P, bsize=bsize, vfp=vtab, search_method=E[mname],
-                         search_sites=cfgs[mname], fast_obmc_search=0,
-                         **dict(zip(MESH_FIELDS[:6], mrow[:6])))
-                    pats = tu.buffer("struct MESH_PATTERN", 4)
-                    for i in range(4):
-                        _set(pats.buf[i], range=mrow[6 + 2 * i], interval=mrow[7 + 2 * i])
-                    # (the set the search reads: mesh_patterns[is_intra_mode])
-                    _get(P, "mesh_patterns")[0] = pats
-                    _get(P, "mesh_patterns")[1] = pats
-                msb = _get(P, "ms_buffers")
-                _set(msb, ref=rbuf, src=sbuf, second_pred=None, mask=None, mask_stride=0,
-                     inv_mask=0, wsrc=None, obmc_mask=None)
-                _set(P, mv_limits=C.copy_obj(L))
-                mcp = _get(P, "mv_cost_params")
-                fref = tu.func("get_fullmv_from_mv")(rmv)
-                _set(mcp, ref_mv=rmv, full_ref_mv=fref, mv_cost_type=E[ctype], mvjcost=mj,
-                     error_per_bit=31 + 7 * (b % 3), sad_per_bit=3 + (b % 4))
-                _get(mcp, "mvcost")[0], _get(mcp, "mvcost")[1] = mc[0], mc[1]
-                pre = "sds" if (skip and bh >= 16) else "sd"
-                vt = vtab.buf[0]
-                _set(P, sdf=_get(vt, "sdsf" if pre == "sds" else "sdf"),
-                     sdx4df=_get(vt, "sdsx4df" if pre == "sds" else "sdx4df"),
-                     sdx3df=_get(vt, "sdsx4df" if pre == "sds" else "sdx3df"))
-                smv = C.new_obj(tu.ctype("FULLPEL_MV"))
-                _set(smv, row=start[0], col=start[1])
-                best = tu.struct_obj("FULLPEL_MV")
-                cl = tu.buffer("int", [0x7FFFFFFF] * 5) if use_cl else None
-                var = tu.func("av1_full_pixel_search")(smv, ms, step_param, cl, best, None)
-                bm = best.buf[0]
+                epb, spb = lambdas(b)
+                off = org + by * stride + bx
+                row, col, var, cl = R.search(bw, bh, mname, use_cl, ctype, skip, step_param, off,
+                                             k, off, ref_mv, start, lims, epb, spb, mrow,
+                                             mesh_thresh)
                 jobs.append([bw, bh, ci, by, bx, k, ref_mv[0], ref_mv[1], start[0], start[1]] +
-                            lims + [_get(mcp, "error_per_bit"), _get(mcp, "sad_per_bit"),
-                                    _get(bm, "row"), _get(bm, "col"), var] +
-                            (list(cl.buf) if use_cl else [0x7FFFFFFF] * 5))
+                            lims + [epb, spb, row, col, var] + cl)
         print("  mcomp %-7s %d jobs" % (sz, len(jobs)))
     out["jobs"] = np.array(jobs, np.int64)
     out["job_fields"] = np.array(["bw", "bh", "case", "by", "bx", "ref", "ref_mv_row",
@@ -798,37 +849,116 @@ SP_SIZES = {(16, 16): 6, (8, 8): 5, (32, 32): 4, (64, 64): 2, (16, 8): 3, (8, 32
             (32, 16): 2, (128, 128): 1, (4, 4): 3}
 
 
+class SubpelRef:
+    """av1_find_best_sub_pixel_tree / _pruned / _pruned_more (av1/encoder/
+    mcomp.c:2907-3126) executed from the reference on planes of the caller's,
+    unscaled reference; tables: the dict of nmv_cost_tables() (hp tables with
+    allow_hp, lp without)."""
+
+    def __init__(self, tables, stride, width, height, border):
+        self.tu = tu = C.TU(REF, ["aom_dsp/variance.c", "av1/encoder/mcomp.c"],
+                            C.reference_defines(REF))
+        check_errors(tu, ["av1_find_best_sub_pixel_tree_pruned_more",
+                          "av1_find_best_sub_pixel_tree_pruned", "av1_find_best_sub_pixel_tree",
+                          "av1_set_subpel_mv_search_range"])
+        self.E = tu.enums
+        self.stride, self.W, self.H, self.BORDER = stride, width, height, border
+        self.tabs = {}
+        for nm in ("lp", "hp"):
+            mj = tu.buffer("int", tables["mvjcost_" + nm].tolist())
+            mc = [tu.buffer("int", tables["mvcost_" + nm][k].tolist()) for k in range(2)]
+            self.tabs[nm] = (mj, [C.Pointer(c.buf, MV_MAX, c.ty) for c in mc])
+        self.mi_params = tu.struct_obj("CommonModeInfoParams")
+        _set(self.mi_params.buf[0], mi_rows=((height + 7) & ~7) // 4,
+             mi_cols=((width + 7) & ~7) // 4)
+        # xd: mi[0] not intrabc, unscaled reference (av1_is_scaled false)
+        self.xd = tu.struct_obj("MACROBLOCKD")
+        mbmi = tu.struct_obj("MB_MODE_INFO")
+        sf = tu.struct_obj("struct scale_factors")
+        _set(sf.buf[0], x_scale_fp=1 << 14, y_scale_fp=1 << 14)
+        _set(self.xd.buf[0], mi=C.Pointer([mbmi], 0, C.Ptr(tu.ctype("MB_MODE_INFO"))))
+        _get(self.xd.buf[0], "block_ref_scale_factors")[0] = sf
+        self.vtabs = {}
+
+    def set_planes(self, src_np, refs_np):
+        self.src_buf = self.tu.buffer("uint8_t", src_np.reshape(-1).tolist())
+        self.ref_bufs = [self.tu.buffer("uint8_t", r.reshape(-1).tolist()) for r in refs_np]
+
+    def vtab(self, bw, bh):
+        if (bw, bh) not in self.vtabs:
+            fn = self.tu.func
+            vtab = self.tu.struct_obj("aom_variance_fn_ptr_t")
+            sz = "%dx%d" % (bw, bh)
+            _set(vtab.buf[0], vf=fn("aom_variance%s" % sz),
+                 svf=fn("aom_sub_pixel_variance%s" % sz))
+            self.vtabs[(bw, bh)] = vtab
+        return self.vtabs[(bw, bh)]
+
+    def search(self, bw, bh, meth, hp, fstop, iters, ctype, cl_vals, epb, src_off, k, ref_off,
+               ref_mv, start, by=None, bx=None, slims=None):
+        """One sub-pel search from `start` (1/8 pel).  The SubpelMvLimits are
+        those of the block at (by, bx) (av1_set_mv_limits then
+        av1_set_subpel_mv_search_range) or `slims` [col_min, col_max,
+        row_min, row_max]; cl_vals: the full-pel cost list or None.  Returns
+        (the limits, best row, best col, besterr, distortion, sse)."""
+        tu, E, stride = self.tu, self.E, self.stride
+        vtab = self.vtab(bw, bh)
+        rmv = tu.struct_obj("MV")
+        _set(rmv.buf[0], row=ref_mv[0], col=ref_mv[1])
+        ms = tu.struct_obj("SUBPEL_MOTION_SEARCH_PARAMS")
+        P = ms.buf[0]
+        sl = _get(P, "mv_limits")
+        if slims is None:
+            lim = tu.struct_obj("FullMvLimits")
+            tu.func("av1_set_mv_limits")(self.mi_params, lim, by // 4, bx // 4, bh // 4, bw // 4,
+                                         self.BORDER)
+            tu.func("av1_set_subpel_mv_search_range")(
+                C.Pointer([sl], 0, tu.ctype("SubpelMvLimits")), lim, rmv)
+            slims = [_get(sl, f) for f in ("col_min", "col_max", "row_min", "row_max")]
+        else:
+            _set(sl, col_min=slims[0], col_max=slims[1], row_min=slims[2], row_max=slims[3])
+        cl = tu.buffer("int", cl_vals) if cl_vals is not None else None
+        _set(P, allow_hp=hp, cost_list=cl, forced_stop=E[fstop], iters_per_step=iters)
+        mcp = _get(P, "mv_cost_params")
+        mj, mc = self.tabs["hp" if hp else "lp"]
+        _set(mcp, ref_mv=rmv, mv_cost_type=E[ctype], mvjcost=mj, error_per_bit=epb,
+             sad_per_bit=0)
+        _get(mcp, "mvcost")[0], _get(mcp, "mvcost")[1] = mc[0], mc[1]
+        vp = _get(P, "var_params")
+        sbuf = tu.struct_obj("struct buf_2d")
+        _set(sbuf.buf[0], buf=C.Pointer(self.src_buf.buf, src_off, C.UCHAR),
+             stride=stride, width=bw, height=bh)
+        rbuf = tu.struct_obj("struct buf_2d")
+        _set(rbuf.buf[0], buf=C.Pointer(self.ref_bufs[k].buf, ref_off, C.UCHAR),
+             stride=stride, width=self.W, height=self.H)
+        # SUBPEL_TREE takes the svf (bilinear) error only with USE_2_TAPS_ORIG
+        _set(vp, vfp=vtab, subpel_search_type=E["USE_2_TAPS_ORIG" if meth == "TREE"
+                                                 else "USE_2_TAPS"], w=bw, h=bh)
+        _set(_get(vp, "ms_buffers"), ref=rbuf, src=sbuf, second_pred=None, mask=None,
+             mask_stride=0, inv_mask=0, wsrc=None, obmc_mask=None)
+        smv = C.new_obj(tu.ctype("MV"))
+        _set(smv, row=start[0], col=start[1])
+        best = tu.struct_obj("MV")
+        dist, sse = tu.buffer("int", 1), tu.buffer("unsigned int", 1)
+        f = "av1_find_best_sub_pixel_tree" + ("" if meth == "TREE" else "_" + meth.lower())
+        err = tu.func(f)(self.xd, None, ms, smv, best, dist, sse, None)
+        bm = best.buf[0]
+        return slims, _get(bm, "row"), _get(bm, "col"), err, dist.buf[0], sse.buf[0]
+
+
 def gen_subpel():
     """av1_find_best_sub_pixel_tree_pruned_more / _pruned (av1/encoder/
     mcomp.c:2907-3126), unscaled reference, starting at full-pel results of
     fix_mcomp.npz with their cost lists, over the entropy (hp tables with
     allow_hp, lp without) / L1 / none mv costs."""
     F = dict(np.load(os.path.join(HERE, "fix_mcomp.npz")))
-    tu = C.TU(REF, ["aom_dsp/variance.c", "av1/encoder/mcomp.c"], C.reference_defines(REF))
-    check_errors(tu, ["av1_find_best_sub_pixel_tree_pruned_more",
-                      "av1_find_best_sub_pixel_tree_pruned", "av1_find_best_sub_pixel_tree",
-                      "av1_set_subpel_mv_search_range"])
-    E = tu.enums
     W, H, BORDER, NREF = (int(v) for v in F["geom"])
     src_np, refs_np = F["src"], F["refs"]
     stride = src_np.shape[1]
     org = BORDER * stride + BORDER
-    src_buf = tu.buffer("uint8_t", src_np.reshape(-1).tolist())
-    ref_bufs = [tu.buffer("uint8_t", r.reshape(-1).tolist()) for r in refs_np]
-    tabs = {}
-    for nm in ("lp", "hp"):
-        mj = tu.buffer("int", F["mvjcost_" + nm].tolist())
-        mc = [tu.buffer("int", F["mvcost_" + nm][k].tolist()) for k in range(2)]
-        tabs[nm] = (mj, [C.Pointer(c.buf, MV_MAX, c.ty) for c in mc])
-    mi_params = tu.struct_obj("CommonModeInfoParams")
-    _set(mi_params.buf[0], mi_rows=((H + 7) & ~7) // 4, mi_cols=((W + 7) & ~7) // 4)
-    # xd: mi[0] not intrabc, unscaled reference (av1_is_scaled false)
-    xd = tu.struct_obj("MACROBLOCKD")
-    mbmi = tu.struct_obj("MB_MODE_INFO")
-    sf = tu.struct_obj("struct scale_factors")
-    _set(sf.buf[0], x_scale_fp=1 << 14, y_scale_fp=1 << 14)
-    _set(xd.buf[0], mi=C.Pointer([mbmi], 0, C.Ptr(tu.ctype("MB_MODE_INFO"))))
-    _get(xd.buf[0], "block_ref_scale_factors")[0] = sf
+    R = SubpelRef(F, stride, W, H, BORDER)
+    E = R.E
+    R.set_planes(src_np, refs_np)
     J = {n: i for i, n in enumerate(F["job_fields"])}
     rnd = ACMRandom(0xbaba + 5)
     picked = {}
@@ -839,57 +969,20 @@ def gen_subpel():
             picked[key].append(r)
     jobs = []
     for (bw, bh), rows in picked.items():
-        fn = tu.func
-        vtab = tu.struct_obj("aom_variance_fn_ptr_t")
         sz = "%dx%d" % (bw, bh)
-        _set(vtab.buf[0], vf=fn("aom_variance%s" % sz), svf=fn("aom_sub_pixel_variance%s" % sz))
         for ci, (meth, hp, fstop, iters, ctype, use_cl) in enumerate(SP_CASES):
             for r in rows[ci % 3::3][:SP_SIZES[(bw, bh)]]:
                 by, bx, k = int(r[J["by"]]), int(r[J["bx"]]), int(r[J["ref"]])
                 ref_mv = (int(r[J["ref_mv_row"]]), int(r[J["ref_mv_col"]]))
-                lim = tu.struct_obj("FullMvLimits")
-                tu.func("av1_set_mv_limits")(mi_params, lim, by // 4, bx // 4, bh // 4, bw // 4,
-                                             BORDER)
-                rmv = tu.struct_obj("MV")
-                _set(rmv.buf[0], row=ref_mv[0], col=ref_mv[1])
-                ms = tu.struct_obj("SUBPEL_MOTION_SEARCH_PARAMS")
-                P = ms.buf[0]
-                tu.func("av1_set_subpel_mv_search_range")(
-                    C.Pointer([_get(P, "mv_limits")], 0, tu.ctype("SubpelMvLimits")), lim, rmv)
-                sl = _get(P, "mv_limits")
-                slims = [_get(sl, f) for f in ("col_min", "col_max", "row_min", "row_max")]
                 cl_vals = [int(v) for v in r[J["cl0"]:J["cl4"] + 1]]
-                cl = tu.buffer("int", cl_vals) if use_cl else None
-                _set(P, allow_hp=hp, cost_list=cl, forced_stop=E[fstop], iters_per_step=iters)
-                mcp = _get(P, "mv_cost_params")
-                mj, mc = tabs["hp" if hp else "lp"]
                 epb = 31 + 11 * rnd.generate(7)
-                _set(mcp, ref_mv=rmv, mv_cost_type=E[ctype], mvjcost=mj, error_per_bit=epb,
-                     sad_per_bit=0)
-                _get(mcp, "mvcost")[0], _get(mcp, "mvcost")[1] = mc[0], mc[1]
-                vp = _get(P, "var_params")
-                sbuf = tu.struct_obj("struct buf_2d")
-                _set(sbuf.buf[0], buf=C.Pointer(src_buf.buf, org + by * stride + bx, C.UCHAR),
-                     stride=stride, width=bw, height=bh)
-                rbuf = tu.struct_obj("struct buf_2d")
-                _set(rbuf.buf[0], buf=C.Pointer(ref_bufs[k].buf, org + by * stride + bx, C.UCHAR),
-                     stride=stride, width=W, height=H)
-                # SUBPEL_TREE takes the svf (bilinear) error only with USE_2_TAPS_ORIG
-                _set(vp, vfp=vtab, subpel_search_type=E["USE_2_TAPS_ORIG" if meth == "TREE"
-                                                         else "USE_2_TAPS"], w=bw, h=bh)
-                _set(_get(vp, "ms_buffers"), ref=rbuf, src=sbuf, second_pred=None, mask=None,
-                     mask_stride=0, inv_mask=0, wsrc=None, obmc_mask=None)
-                smv = C.new_obj(tu.ctype("MV"))
                 start = (int(r[J["best_row"]]) * 8, int(r[J["best_col"]]) * 8)
-                _set(smv, row=start[0], col=start[1])
-                best = tu.struct_obj("MV")
-                dist, sse = tu.buffer("int", 1), tu.buffer("unsigned int", 1)
-                f = "av1_find_best_sub_pixel_tree" + ("" if meth == "TREE" else "_" + meth.lower())
-                err = tu.func(f)(xd, None, ms, smv, best, dist, sse, None)
-                bm = best.buf[0]
+                off = org + by * stride + bx
+                slims, row, col, err, dist, sse = R.search(
+                    bw, bh, meth, hp, fstop, iters, ctype, cl_vals if use_cl else None, epb, off,
+                    k, off, ref_mv, start, by, bx)
                 jobs.append([bw, bh, ci, by, bx, k, ref_mv[0], ref_mv[1], start[0], start[1]] +
-                            slims + [epb, _get(bm, "row"), _get(bm, "col"), err, dist.buf[0],
-                                     sse.buf[0]] + cl_vals)
+                            slims + [epb, row, col, err, dist, sse] + cl_vals)
         print("  subpel %-7s %d jobs" % (sz, len(jobs)))
     out = {"jobs": np.array(jobs, np.int64)}
     out["job_fields"] = np.array(["bw", "bh", "case", "by", "bx", "ref", "ref_mv_row",

@@ -144,3 +144,39 @@ def test_interp_extremes_rederived():
                c.p_width, c.p_height)
         np.testing.assert_array_equal(wp.pred[-1].reshape(c.pred.shape), c.pred, err_msg=str(k))
         np.testing.assert_array_equal(wp.buf[-1].reshape(c.buf.shape), c.buf, err_msg=str(k))
+
+
+def test_mcomp_extremes_rederived():
+    """fix_mcomp_extremes: one full-pel case of each family (a flat tie, a
+    ramp, a periodic tile, a single-point window, a saturated 16x16 block,
+    the lowest and the highest lambda) and three sub-pel cases (a cost list, a limit edge, a
+    high lambda) re-executed from the reference on the stored planes."""
+    sys.path.insert(0, GOLD)
+    import gen_fix_mcomp_extremes as GM
+    import _mvextremes as X
+    from lavish_dsp import motion as M
+    F = X.load_fixture()
+    t = {}     # (the package's tables: gen_fix_mcomp_extremes checks them when it runs)
+    for hp, nm in ((False, "lp"), (True, "hp")):
+        t["mvjcost_" + nm], t["mvcost_" + nm] = M.default_mv_cost_tables(hp)
+    for which, run, want in (
+            ("fp", GM.fullpel_rows, ["flat_255_0", "ramp_x", "periodic_8", "point", "sat69",
+                                     "lambda71", "lambda77"]),
+            ("sp", GM.subpel_rows, ["sub_tie", "edge", "sub_lambda71"])):
+        names = [str(n) for n in F[which + "_names"]]
+        kinds = [str(k) for k in F[which + "_kinds"]]
+        fp = {c.name: c for c in X.fixture_fullpel()}
+        if which == "sp":
+            cases = {c.name: c for c in X.fixture_subpel(
+                GM.fullpel_results(list(fp.values()), F["fp_rows"]))}
+        else:
+            cases = fp
+        picks = []
+        for w in want:
+            m = [i for i, (n, k) in enumerate(zip(names, kinds)) if n.startswith(w) or k == w]
+            assert m, w
+            picks.append(m[0])
+        rows = run(t, {}, [(i, cases[names[i]]) for i in picks])
+        stored = F[which + "_rows"]
+        stored = np.concatenate([stored[stored[:, 0] == i] for i in picks])
+        np.testing.assert_array_equal(rows, stored)
