@@ -394,6 +394,122 @@ def results_numpy(out):
     return out.cpu().numpy().view(RESULT_DTYPE)
 
 
+# ------------------------------------- compound / masked / OBMC full-pel --
+COMP_JOB_DTYPE = np.dtype([("base", JOB_DTYPE), ("second_off", "<i8"), ("mask_off", "<i8"),
+                           ("invert_mask", "<i4"), ("reserved", "<i4")], align=True)
+COMP_RESULT_DTYPE = np.dtype([("best_row", "<i2"), ("best_col", "<i2"), ("second_row", "<i2"),
+                              ("second_col", "<i2"), ("bestsme", "<i4"), ("steps", "<i4")],
+                             align=True)
+assert COMP_JOB_DTYPE.itemsize == 56 and COMP_RESULT_DTYPE.itemsize == 16
+INVALID_MV = -32768   # second_row / second_col of a search that never moved
+
+_lib.lavish_comp_full_pixel_search_batch.argtypes = [
+    _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, ctypes.POINTER(MvCostParams), _vp,
+    _vp, _i32, _vp, _vp]
+_lib.lavish_comp_full_pixel_search_batch.restype = _i32
+_lib.lavish_refining_search_8p_batch.argtypes = [
+    _vp, _i32, _vp, _i32, _i32, _i32, _vp, _i32, ctypes.POINTER(MvCostParams), _vp, _vp, _i32,
+    _vp, _vp]
+_lib.lavish_refining_search_8p_batch.restype = _i32
+_lib.lavish_obmc_full_pixel_search_batch.argtypes = [
+    _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, ctypes.POINTER(MvCostParams), _i32, _vp, _vp,
+    _vp, _vp]
+_lib.lavish_obmc_full_pixel_search_batch.restype = _i32
+
+
+def comp_jobs(jobs, second_off, mask_off=0, invert_mask=0):
+    """COMP_JOB_DTYPE records from JOB_DTYPE ones: second_off the job's
+    second_pred block (u8 elements, stride w; OBMC: its wsrc block, int32
+    elements), mask_off its mask block (u8, mask_stride; OBMC: int32);
+    scalars or one value per job."""
+    out = np.zeros(len(jobs), COMP_JOB_DTYPE)
+    out["base"] = jobs
+    out["second_off"], out["mask_off"], out["invert_mask"] = second_off, mask_off, invert_mask
+    return out
+
+
+def _comp_out(nj, out, device):
+    import torch
+    if out is None:
+        out = torch.empty(nj * COMP_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=device)
+    assert out.numel() >= nj * COMP_RESULT_DTYPE.itemsize
+    return out
+
+
+def _ptr(t, dtype):
+    import torch
+    if t is None:
+        return None
+    assert t.dtype == dtype and t.is_contiguous()
+    return _vp(t.data_ptr())
+
+
+def comp_full_pixel_search_batch(src, ref, w, h, jobs, cost, second_pred, mask=None,
+                                 mask_stride=0, method="diamond", step_param=0, out=None,
+                                 stream=None):
+    """lavish_comp_full_pixel_search_batch (av1_full_pixel_search with
+    ms_buffers.second_pred, DIAMOND / NSTEP / NSTEP_8PT): planes as
+    full_pixel_search_batch, jobs a device byte tensor of COMP_JOB_DTYPE
+    records, second_pred (and mask, or None for the average) uint8 device
+    tensors the jobs' offsets index.  Returns a device byte tensor of
+    COMP_RESULT_DTYPE records (view with comp_results_numpy)."""
+    import torch
+    assert src.dtype == torch.uint8 and ref.dtype == torch.uint8
+    assert src.is_contiguous() and ref.is_contiguous(), "planes must be C-contiguous"
+    nj = jobs.numel() // COMP_JOB_DTYPE.itemsize
+    out = _comp_out(nj, out, src.device)
+    rc = _lib.lavish_comp_full_pixel_search_batch(
+        _vp(src.data_ptr()), src.stride(0), _vp(ref.data_ptr()), src.stride(0), w, h,
+        _vp(jobs.data_ptr()), nj, SEARCH_METHODS[method], step_param, ctypes.byref(cost),
+        _ptr(second_pred, torch.uint8), _ptr(mask, torch.uint8), mask_stride,
+        _vp(out.data_ptr()), _stream_ptr(stream))
+    if rc != 0:
+        raise ValueError("lavish_comp_full_pixel_search_batch rejected its arguments (rc=%d)" % rc)
+    return out
+
+
+def refining_search_8p_batch(src, ref, w, h, jobs, cost, second_pred=None, mask=None,
+                             mask_stride=0, out=None, stream=None):
+    """lavish_refining_search_8p_batch (av1_refining_search_8p_c): as
+    comp_full_pixel_search_batch; second_pred None: the plain SAD.  bestsme
+    is the search's best_sad (SAD + mv SAD cost)."""
+    import torch
+    assert src.dtype == torch.uint8 and ref.dtype == torch.uint8
+    assert src.is_contiguous() and ref.is_contiguous(), "planes must be C-contiguous"
+    nj = jobs.numel() // COMP_JOB_DTYPE.itemsize
+    out = _comp_out(nj, out, src.device)
+    rc = _lib.lavish_refining_search_8p_batch(
+        _vp(src.data_ptr()), src.stride(0), _vp(ref.data_ptr()), src.stride(0), w, h,
+        _vp(jobs.data_ptr()), nj, ctypes.byref(cost), _ptr(second_pred, torch.uint8),
+        _ptr(mask, torch.uint8), mask_stride, _vp(out.data_ptr()), _stream_ptr(stream))
+    if rc != 0:
+        raise ValueError("lavish_refining_search_8p_batch rejected its arguments (rc=%d)" % rc)
+    return out
+
+
+def obmc_full_pixel_search_batch(ref, ref_stride, w, h, jobs, cost, wsrc, obmc_mask,
+                                 method="diamond", step_param=0, fast_obmc_search=False,
+                                 out=None, stream=None):
+    """lavish_obmc_full_pixel_search_batch (av1_obmc_full_pixel_search): ref
+    the uint8 reference planes, wsrc / obmc_mask int32 device tensors the
+    jobs' second_off / mask_off index (in int32 elements; src_off is unused)."""
+    import torch
+    assert ref.dtype == torch.uint8 and ref.is_contiguous(), "planes must be C-contiguous"
+    nj = jobs.numel() // COMP_JOB_DTYPE.itemsize
+    out = _comp_out(nj, out, ref.device)
+    rc = _lib.lavish_obmc_full_pixel_search_batch(
+        _vp(ref.data_ptr()), ref_stride, w, h, _vp(jobs.data_ptr()), nj, SEARCH_METHODS[method],
+        step_param, ctypes.byref(cost), int(fast_obmc_search), _ptr(wsrc, torch.int32),
+        _ptr(obmc_mask, torch.int32), _vp(out.data_ptr()), _stream_ptr(stream))
+    if rc != 0:
+        raise ValueError("lavish_obmc_full_pixel_search_batch rejected its arguments (rc=%d)" % rc)
+    return out
+
+
+def comp_results_numpy(out):
+    return out.cpu().numpy().view(COMP_RESULT_DTYPE)
+
+
 # ------------------------------------------------------- sub-pixel search --
 SUBPEL_JOB_DTYPE = np.dtype([("src_off", "<i8"), ("ref_off", "<i8"), ("start_row", "<i2"),
                              ("start_col", "<i2"), ("ref_mv_row", "<i2"), ("ref_mv_col", "<i2"),

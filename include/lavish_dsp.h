@@ -736,6 +736,77 @@ int lavish_full_pixel_search_batch_mesh(const uint8_t *src, int src_stride,
                                         LavishDiamondResult *out, int32_t *cost_lists,
                                         void *stream);
 
+/* The compound, masked and OBMC full-pel searches (csrc/mcomp_comp.hip),
+ * 8-bit, one wave per job.  A job is a LavishDiamondJob plus where its
+ * job-invariant blocks lie in the buffers the call takes: second_pred
+ * (compact, stride w) and the blend mask (rows mask_stride apart), or for
+ * OBMC the int32 wsrc / mask blocks (compact, offsets in int32 elements;
+ * base.src_off is not read). */
+typedef struct LavishCompSearchJob { /* 56 bytes */
+  LavishDiamondJob base; /* offsets, start, ref_mv, limits: as today */
+  int64_t second_off; /* second_pred block, u8, stride w; OBMC: wsrc block (int32, w*h) */
+  int64_t mask_off;   /* u8 mask block (mask_stride); OBMC: int32 mask block (w*h) */
+  int32_t invert_mask; /* masked form: nonzero swaps the blend operands */
+  int32_t reserved;
+} LavishCompSearchJob;
+
+typedef struct LavishCompSearchResult { /* 16 bytes */
+  int16_t best_row, best_col;
+  int16_t second_row, second_col; /* -32768, -32768: invalid */
+  int32_t bestsme; /* the full-pel and OBMC searches: var + mv cost; the
+                      8-point refinement: best_sad */
+  int32_t steps;   /* step / round iterations executed over all runs */
+} LavishCompSearchResult;
+
+/* av1_full_pixel_search (mcomp.c:1755-1895) with ms_buffers.second_pred set,
+ * search_method DIAMOND 0, NSTEP 1 or NSTEP_8PT 2: diamond_search_sad's
+ * second_pred branch (:1377-1405, sites one at a time, msdf when `mask` is
+ * given, else sdaf) under full_pixel_diamond (:1479-1526), the cost of each
+ * run get_mvpred_compound_var_cost (:695-727: msvf / svaf at sub-pel offset
+ * (0, 0)); no mesh (:1822), no cost list.  second_row / second_col: the
+ * reference's second_best_mv, as it leaves it (the position the last move
+ * of the last run left; invalid when no run moved).  There is no
+ * use_downsampled_sad argument: with second_pred the walk never reads sdf,
+ * so the quality recheck has nothing to check.  second_pred / mask:
+ * device; mask NULL: the rounded average.  Returns 0, -1 bad step_param,
+ * -2 bad cost parameters, -3 unsupported w x h, -4 a method outside the
+ * three, -7 a NULL buffer or mask_stride < w. */
+int lavish_comp_full_pixel_search_batch(const uint8_t *src, int src_stride,
+                                        const uint8_t *ref, int ref_stride, int w,
+                                        int h, const LavishCompSearchJob *jobs,
+                                        int njobs, int search_method, int step_param,
+                                        const LavishMvCostParams *cost,
+                                        const uint8_t *second_pred, const uint8_t *mask,
+                                        int mask_stride, LavishCompSearchResult *out,
+                                        void *stream);
+
+/* av1_refining_search_8p_c (mcomp.c:1683-1753): from the clamped start up to
+ * 3 rounds over the 8 neighbours not yet visited, the SAD
+ * get_mvpred_compound_sad (second_pred NULL: the plain sdf; mask NULL: sdaf).
+ * bestsme = best_sad (SAD + mv SAD cost); second_row / second_col repeat the
+ * best mv.  Returns as above. */
+int lavish_refining_search_8p_batch(const uint8_t *src, int src_stride,
+                                    const uint8_t *ref, int ref_stride, int w, int h,
+                                    const LavishCompSearchJob *jobs, int njobs,
+                                    const LavishMvCostParams *cost,
+                                    const uint8_t *second_pred, const uint8_t *mask,
+                                    int mask_stride, LavishCompSearchResult *out,
+                                    void *stream);
+
+/* av1_obmc_full_pixel_search (mcomp.c:2328-2342): fast_obmc_search 0
+ * obmc_full_pixel_diamond (:2293-2326) over the sites of search_method (as
+ * above), else obmc_refining_search_sad (:2190-2233; search_method and
+ * step_param are still checked); the SAD osdf, the cost get_obmc_mvpred_var
+ * (ovf + mv cost).  wsrc / obmc_mask: device int32.  second_row /
+ * second_col are invalid.  Returns as above. */
+int lavish_obmc_full_pixel_search_batch(const uint8_t *ref, int ref_stride, int w, int h,
+                                        const LavishCompSearchJob *jobs, int njobs,
+                                        int search_method, int step_param,
+                                        const LavishMvCostParams *cost,
+                                        int fast_obmc_search, const int32_t *wsrc,
+                                        const int32_t *obmc_mask,
+                                        LavishCompSearchResult *out, void *stream);
+
 /* C2 and the C3 search in one launch: lavish_txq_frame(residual, ...) and
  * lavish_full_pixel_search_batch_tiled(src, ..., 16, 16, jobs, njobs,
  * DIAMOND, ...) with the same results, run as one grid (the 64-point sizes
