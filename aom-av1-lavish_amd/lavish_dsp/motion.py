@@ -644,3 +644,104 @@ def find_best_sub_pixel_tree_batch(src, ref, w, h, jobs, cost, method="pruned_mo
 
 def subpel_results_numpy(out):
     return out.cpu().numpy().view(SUBPEL_RESULT_DTYPE)
+
+
+# ------------------------------------- compound / masked / OBMC sub-pel ----
+COMP_SUBPEL_JOB_DTYPE = np.dtype([("base", SUBPEL_JOB_DTYPE), ("second_off", "<i8"),
+                                  ("mask_off", "<i8"), ("invert_mask", "<i4"),
+                                  ("reserved", "<i4")], align=True)
+assert COMP_SUBPEL_JOB_DTYPE.itemsize == 56
+
+_lib.lavish_comp_find_best_sub_pixel_tree_batch.argtypes = [
+    _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+    ctypes.POINTER(MvCostParams), _vp, _vp, _i32, _vp, _vp]
+_lib.lavish_comp_find_best_sub_pixel_tree_batch.restype = _i32
+_lib.lavish_obmc_find_best_sub_pixel_tree_batch.argtypes = [
+    _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, ctypes.POINTER(MvCostParams),
+    _vp, _vp, _vp, _vp]
+_lib.lavish_obmc_find_best_sub_pixel_tree_batch.restype = _i32
+
+
+def comp_subpel_jobs(subpel_jobs, second_off, mask_off=0, invert_mask=0):
+    """COMP_SUBPEL_JOB_DTYPE records from SUBPEL_JOB_DTYPE ones: the offsets
+    and invert_mask as comp_jobs takes them; scalars or one value per job."""
+    out = np.zeros(len(subpel_jobs), COMP_SUBPEL_JOB_DTYPE)
+    out["base"] = subpel_jobs
+    out["second_off"], out["mask_off"], out["invert_mask"] = second_off, mask_off, invert_mask
+    return out
+
+
+def _subpel_out(nj, out, device):
+    import torch
+    if out is None:
+        out = torch.empty(nj * SUBPEL_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=device)
+    assert out.numel() >= nj * SUBPEL_RESULT_DTYPE.itemsize
+    return out
+
+
+def comp_find_best_sub_pixel_tree_batch(src, ref, w, h, jobs, cost, second_pred, mask=None,
+                                        mask_stride=0, method="pruned_more",
+                                        search_type=USE_2_TAPS_ORIG, forced_stop=EIGHTH_PEL,
+                                        allow_hp=False, iters_per_step=1, fullpel=None,
+                                        start_from=0, out=None, stream=None):
+    """lavish_comp_find_best_sub_pixel_tree_batch: the sub-pel search with
+    ms_buffers.second_pred (and mask, or None for the average); jobs a device
+    byte tensor of COMP_SUBPEL_JOB_DTYPE records.  fullpel: the device
+    COMP_RESULT_DTYPE bytes of comp_full_pixel_search_batch /
+    refining_search_8p_batch to start from (start_from 0 the best mv, 1 the
+    second-best: jobs without a usable one return besterr INT_MAX and mv
+    INVALID_MV), or None for the jobs' start fields.  Returns a device byte
+    tensor of SUBPEL_RESULT_DTYPE records."""
+    import torch
+    assert src.dtype == torch.uint8 and ref.dtype == torch.uint8
+    assert src.is_contiguous() and ref.is_contiguous(), "planes must be C-contiguous"
+    nj = jobs.numel() // COMP_SUBPEL_JOB_DTYPE.itemsize
+    if fullpel is not None:
+        assert fullpel.numel() >= nj * COMP_RESULT_DTYPE.itemsize
+    out = _subpel_out(nj, out, src.device)
+    rc = _lib.lavish_comp_find_best_sub_pixel_tree_batch(
+        _vp(src.data_ptr()), src.stride(0), _vp(ref.data_ptr()), src.stride(0), w, h,
+        _vp(jobs.data_ptr()), None if fullpel is None else _vp(fullpel.data_ptr()), start_from,
+        nj, SUBPEL_METHODS[method], search_type, forced_stop, int(allow_hp), iters_per_step,
+        ctypes.byref(cost), _ptr(second_pred, torch.uint8), _ptr(mask, torch.uint8), mask_stride,
+        _vp(out.data_ptr()), _stream_ptr(stream))
+    if rc != 0:
+        raise ValueError("lavish_comp_find_best_sub_pixel_tree_batch rejected its arguments "
+                         "(rc=%d)" % rc)
+    return out
+
+
+def obmc_find_best_sub_pixel_tree_batch(ref, ref_stride, w, h, jobs, cost, wsrc, obmc_mask,
+                                        search_type=USE_2_TAPS_ORIG, forced_stop=EIGHTH_PEL,
+                                        allow_hp=False, iters_per_step=1, fullpel=None, out=None,
+                                        stream=None):
+    """lavish_obmc_find_best_sub_pixel_tree_batch
+    (av1_find_best_obmc_sub_pixel_tree_up): ref / wsrc / obmc_mask as
+    obmc_full_pixel_search_batch, jobs COMP_SUBPEL_JOB_DTYPE records, fullpel
+    the bytes obmc_full_pixel_search_batch returned (or None)."""
+    import torch
+    assert ref.dtype == torch.uint8 and ref.is_contiguous(), "planes must be C-contiguous"
+    nj = jobs.numel() // COMP_SUBPEL_JOB_DTYPE.itemsize
+    if fullpel is not None:
+        assert fullpel.numel() >= nj * COMP_RESULT_DTYPE.itemsize
+    out = _subpel_out(nj, out, ref.device)
+    rc = _lib.lavish_obmc_find_best_sub_pixel_tree_batch(
+        _vp(ref.data_ptr()), ref_stride, w, h, _vp(jobs.data_ptr()),
+        None if fullpel is None else _vp(fullpel.data_ptr()), nj, search_type, forced_stop,
+        int(allow_hp), iters_per_step, ctypes.byref(cost), _ptr(wsrc, torch.int32),
+        _ptr(obmc_mask, torch.int32), _vp(out.data_ptr()), _stream_ptr(stream))
+    if rc != 0:
+        raise ValueError("lavish_obmc_find_best_sub_pixel_tree_batch rejected its arguments "
+                         "(rc=%d)" % rc)
+    return out
+
+
+def pick_lower_besterr(a, b):
+    """Of two device byte tensors of SUBPEL_RESULT_DTYPE records, per job the
+    record of `a` unless b's besterr is strictly lower
+    (motion_search_facade.c:670); stays on the device."""
+    import torch
+    ra, rb = a.view(torch.int32).view(-1, 4), b.view(torch.int32).view(-1, 4)
+    # besterr is uint32 at most INT_MAX + a small mv cost: compare as unsigned
+    ea, eb = ra[:, 1].to(torch.int64) & 0xFFFFFFFF, rb[:, 1].to(torch.int64) & 0xFFFFFFFF
+    return torch.where((eb < ea)[:, None], rb, ra).contiguous().view(torch.uint8).view(-1)

@@ -936,6 +936,69 @@ int lavish_find_best_sub_pixel_tree_batch_ex(
     int allow_hp, int iters_per_step, const LavishMvCostParams *cost,
     const int32_t *cost_lists, LavishSubpelResult *out, void *stream);
 
+/* The compound, masked and OBMC sub-pel searches (csrc/subpel_comp.hip),
+ * 8-bit, unscaled reference, one wave per job: what follows
+ * lavish_comp_full_pixel_search_batch / lavish_refining_search_8p_batch in
+ * av1_joint_motion_search and av1_compound_single_motion_search
+ * (motion_search_facade.c:642-676, 786-793) and
+ * lavish_obmc_full_pixel_search_batch in av1_single_motion_search's
+ * OBMC_CAUSAL leg (:441-445).  A job is a LavishSubpelJob plus where its
+ * job-invariant blocks lie, as in LavishCompSearchJob. */
+typedef struct LavishCompSubpelJob { /* 56 bytes */
+  LavishSubpelJob base; /* offsets, start (1/8 pel), ref mv, SubpelMvLimits: as today */
+  int64_t second_off; /* second_pred block, u8, stride w; OBMC: wsrc block (int32, w*h) */
+  int64_t mask_off;   /* u8 mask block (mask_stride); OBMC: int32 mask block (w*h) */
+  int32_t invert_mask;
+  int32_t reserved;
+} LavishCompSubpelJob;
+
+/* av1_find_best_sub_pixel_tree (mcomp.c:3128-3196), _pruned (:2992-3126) or
+ * _pruned_more (:2907-2990) with ms_buffers.second_pred set, cost_list and
+ * last_mv_search_list NULL as the encoder passes them on this path (the
+ * pruned methods therefore start with two_level_checks_fast).  The centre
+ * error is setup_center_error's second_pred branch (aom_comp_avg_pred /
+ * aom_comp_mask_pred of the block at the start's full-pel floor, then vf);
+ * the candidates estimated_pref_error (svaf, or msvf with `mask`), and for
+ * SUBPEL_TREE with a subpel_search_type other than USE_2_TAPS_ORIG
+ * upsampled_pref_error's second_pred branches (the centre then at the start
+ * itself).  Methods, types, forced_stop, iters_per_step and cost as
+ * lavish_find_best_sub_pixel_tree_batch_ex.  second_pred / mask: device;
+ * mask NULL: the rounded average.
+ * fullpel (device, or NULL to use the jobs' start fields): the results of
+ * one of the three full-pel calls above for the same jobs; start_from 0
+ * starts at best x 8, start_from 1 at second x 8 (the try_second call,
+ * motion_search_facade.c:663-669).  With start_from 1 a job whose second mv
+ * is invalid (-32768) or outside the job's SubpelMvLimits is not searched:
+ * its record is besterr INT_MAX, best_row = best_col = -32768, distortion
+ * and sse 0; the caller keeps the lower besterr.
+ * Returns 0 (also njobs <= 0: nothing done), -1 bad forced_stop, -2 bad cost
+ * parameters, -3 unsupported w x h, -4 bad iters_per_step, -6 bad method,
+ * -7 bad search type, -8 a NULL buffer, mask_stride < w with a mask or
+ * start_from outside 0 / 1, -9 start_from 1 without fullpel; every refusal
+ * before any device work. */
+int lavish_comp_find_best_sub_pixel_tree_batch(
+    const uint8_t *src, int src_stride, const uint8_t *ref, int ref_stride, int w, int h,
+    const LavishCompSubpelJob *jobs, const LavishCompSearchResult *fullpel, int start_from,
+    int njobs, int subpel_search_method, int subpel_search_type, int forced_stop, int allow_hp,
+    int iters_per_step, const LavishMvCostParams *cost, const uint8_t *second_pred,
+    const uint8_t *mask, int mask_stride, LavishSubpelResult *out, void *stream);
+
+/* av1_find_best_obmc_sub_pixel_tree_up (mcomp.c:3761-3803): the errors osvf
+ * (USE_2_TAPS_ORIG) or aom_upsampled_pred_c then ovf.  As the reference:
+ * with USE_2_TAPS_ORIG the centre error is read at mv (0, 0), not at the
+ * start (setup_obmc_center_error, :3530-3545; the mv cost is the start's),
+ * and the candidates are priced by estimate_obmc_mvcost (:3561-3583: the
+ * rate of the diff x 8, (rate * error_per_bit + 4096) >> 13; 0 for
+ * MV_COST_NONE); the other types use mv_err_cost_ and the start.  wsrc /
+ * obmc_mask: device int32; base.src_off is not read.  fullpel: the results
+ * of lavish_obmc_full_pixel_search_batch, or NULL.  Returns as above, and
+ * -2 for an L1 cost type with USE_2_TAPS_ORIG (the reference asserts). */
+int lavish_obmc_find_best_sub_pixel_tree_batch(
+    const uint8_t *ref, int ref_stride, int w, int h, const LavishCompSubpelJob *jobs,
+    const LavishCompSearchResult *fullpel, int njobs, int subpel_search_type, int forced_stop,
+    int allow_hp, int iters_per_step, const LavishMvCostParams *cost, const int32_t *wsrc,
+    const int32_t *obmc_mask, LavishSubpelResult *out, void *stream);
+
 /* ---- Inter prediction -----------------------------
  * av1_enc_build_one_inter_predictor (av1/encoder/reconinter_enc.c:47-51) for
  * a batch of single-reference translational blocks: init_subpel_params
