@@ -51,34 +51,14 @@ struct SJob {
 static_assert(sizeof(SJob) == sizeof(LavishSubpelJob), "job layout");
 static_assert(sizeof(LavishSubpelResult) == 16, "result layout");
 
-struct SpCtx {
+struct SpCtx : MvCtx {
+  int up_kind;  // -1: the bilinear svf error; else kUpK kind of the upsampled error
+  int ss, rs;
   const uint8_t* src;
   const uint8_t* ref;
-  int ss, rs;
-  int ref_mv_row, ref_mv_col;
-  int col_min, col_max, row_min, row_max;
-  int lambda;  // mv_err_cost_ L1 lambda (0: MV_COST_NONE)
-  int up_kind;  // -1: the bilinear svf error; else kUpK kind of the upsampled error
-  bool entropy;
-  int error_per_bit;
-  const int32_t* mvjcost;
-  const int32_t* mvcost0;  // centred at MV_MAX
-  const int32_t* mvcost1;
 };
-
-// mv_err_cost_ (mcomp.c:290-323) at a wave-uniform mv
-__device__ __forceinline__ int mv_cost(const SpCtx& c, int row, int col) {
-  const int dr = row - c.ref_mv_row, dc = col - c.ref_mv_col;
-  if (c.entropy) {
-    const int joint = (dc != 0) | ((dr != 0) << 1);  // av1_get_mv_joint
-    const int rate = c.mvjcost[joint] + c.mvcost0[dr] + c.mvcost1[dc];
-    return (int)(((int64_t)rate * c.error_per_bit + 8192) >> 14);
-  }
-  return (c.lambda * (abs(dr) + abs(dc))) >> 3;
-}
-__device__ __forceinline__ bool in_range(const SpCtx& c, int row, int col) {
-  return col >= c.col_min && col <= c.col_max && row >= c.row_min && row <= c.row_max;
-}
+// seg_err_up takes it through memory: its size is scratch in every instantiation
+static_assert(sizeof(SpCtx) == 88, "context size");
 
 __device__ __forceinline__ void seg4(const SpCtx& c, const uint8_t* base, int y, int x,
                                      uint32_t sw, int f0, int f1, int g0, int g1, int& sum,
@@ -203,119 +183,10 @@ __device__ __forceinline__ int div_round(int n, int d) {
   return ((n < 0) ^ (d < 0)) ? ((n - d / 2) / d) : ((n + d / 2) / d);
 }
 
-// evaluate up to 4 candidates (wave-uniform mvs), then the sequential
-// check_better_fast updates; returns each candidate's cost (INT_MAX when out
-// of range) through cost[]
-template <int W, int H, int N>
-__device__ __forceinline__ void check_n(const SpCtx& c, const uint32_t (&sv)[Sp<W, H>::NS],
-                                        int lane, const int (&r)[N], const int (&cl)[N],
-                                        Best& b, uint32_t (&cost)[N]) {
-  int sum[N];
-  uint32_t sse[N];
-  bool ok[N];
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    sum[k] = 0;
-    sse[k] = 0;
-    ok[k] = in_range(c, r[k], cl[k]);
-    if (ok[k]) seg_err<W, H>(c, sv, lane, r[k], cl[k], sum[k], sse[k]);
-  }
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    cost[k] = 0x7FFFFFFFu;  // INT_MAX
-    if (!ok[k]) continue;
-    const int ts = (int)wave_total((uint32_t)sum[k]);
-    const uint32_t tq = wave_total(sse[k]);
-    const uint32_t var = tq - (uint32_t)(((int64_t)ts * ts) / (W * H));
-    cost[k] = (uint32_t)mv_cost(c, r[k], cl[k]) + var;
-    if (cost[k] < b.besterr) {
-      b.besterr = cost[k];
-      b.row = r[k];
-      b.col = cl[k];
-      b.distortion = (int)var;
-      b.sse1 = tq;
-    }
-  }
-}
-
-template <int W, int H>
-__device__ void two_level(const SpCtx& c, const uint32_t (&sv)[Sp<W, H>::NS], int lane, int tr,
-                          int tc, int hstep, int iters, Best& b) {
-  uint32_t cst[4];
-  {
-    const int r[4] = {tr, tr, tr - hstep, tr + hstep};
-    const int cl[4] = {tc - hstep, tc + hstep, tc, tc};
-    check_n<W, H, 4>(c, sv, lane, r, cl, b, cst);
-  }
-  // get_best_diag_step: toward the cheaper of up/down and left/right
-  const int dr = cst[2] <= cst[3] ? -hstep : hstep;
-  const int dc = cst[0] <= cst[1] ? -hstep : hstep;
-  uint32_t d1[1];
-  {
-    const int r[1] = {tr + dr};
-    const int cl[1] = {tc + dc};
-    check_n<W, H, 1>(c, sv, lane, r, cl, b, d1);
-  }
-  if (iters <= 1) return;
-  const int br = b.row, bc = b.col;
-  if (tr != br && tc != bc) {
-    const int r[2] = {br, br + dr};
-    const int cl[2] = {bc + dc, bc};
-    uint32_t d2[2];
-    check_n<W, H, 2>(c, sv, lane, r, cl, b, d2);
-  } else if (tr == br && tc != bc) {
-    const int r[3] = {br + hstep, br - hstep, br - dr};
-    const int cl[3] = {bc + dc, bc + dc, bc};
-    uint32_t d3[3];
-    check_n<W, H, 3>(c, sv, lane, r, cl, b, d3);
-  } else if (tr != br && tc == bc) {
-    const int r[3] = {br + dr, br + dr, br};
-    const int cl[3] = {bc + hstep, bc - hstep, bc - dc};
-    uint32_t d3[3];
-    check_n<W, H, 3>(c, sv, lane, r, cl, b, d3);
-  }
-}
-
-// one SUBPEL_TREE level with the bilinear error (USE_2_TAPS_ORIG):
-// first_level_check_fast (mcomp.c:2566-2606) around the current best, then
-// with iters_per_step > 1 and a moved best second_level_check_v2
-// (:2728-2779): row / column bias points away from a losing diagonal, the
-// diagonal bias point only when one of them improved
-template <int W, int H>
-__device__ void tree_level(const SpCtx& c, const uint32_t (&sv)[Sp<W, H>::NS], int lane,
-                           int hstep, int iters, Best& b) {
-  const int tr = b.row, tc = b.col;
-  uint32_t cst[4];
-  {
-    const int r[4] = {tr, tr, tr - hstep, tr + hstep};
-    const int cl[4] = {tc - hstep, tc + hstep, tc, tc};
-    check_n<W, H, 4>(c, sv, lane, r, cl, b, cst);
-  }
-  int dr = cst[2] <= cst[3] ? -hstep : hstep;
-  int dc = cst[0] <= cst[1] ? -hstep : hstep;
-  uint32_t d1[1];
-  {
-    const int r[1] = {tr + dr};
-    const int cl[1] = {tc + dc};
-    check_n<W, H, 1>(c, sv, lane, r, cl, b, d1);
-  }
-  if (iters <= 1) return;
-  const int br = b.row, bc = b.col;
-  if (br == tr && bc == tc) return;
-  if (tr == br) dr = -dr;
-  else if (tc == bc) dc = -dc;
-  const uint32_t before = b.besterr;
-  {
-    const int r[2] = {br + dr, br};
-    const int cl[2] = {bc, bc + dc};
-    uint32_t d2[2];
-    check_n<W, H, 2>(c, sv, lane, r, cl, b, d2);
-  }
-  if (b.besterr != before) {
-    const int r[1] = {br + dr};
-    const int cl[1] = {bc + dc};
-    check_n<W, H, 1>(c, sv, lane, r, cl, b, d1);
-  }
+// a candidate's price: mv_err_cost_
+template <int N>
+__device__ __forceinline__ int cand_cost(const SpCtx& c, const uint32_t (&)[N], int row, int col) {
+  return mv_cost(c, row, col);
 }
 
 template <int W, int H>
@@ -339,20 +210,8 @@ __global__ __launch_bounds__(256) void subpel_kernel(const uint8_t* __restrict__
   c.ref = ref + jb.ref_off;
   c.ss = ss;
   c.rs = rs;
-  c.ref_mv_row = jb.ref_mv_row;
-  c.ref_mv_col = jb.ref_mv_col;
-  c.col_min = jb.col_min;
-  c.col_max = jb.col_max;
-  c.row_min = jb.row_min;
-  c.row_max = jb.row_max;
-  // mv_err_cost_ lambdas: SSE_LAMBDA_LOWRES 2, MIDRES 0, HDRES 1; NONE 0
-  c.lambda = cost.mv_cost_type == 1 ? 2 : cost.mv_cost_type == 3 ? 1 : 0;
+  fill_mv_ctx(c, jb, cost);
   c.up_kind = method == 0 ? up_kind : -1;  // only SUBPEL_TREE takes the upsampled error
-  c.entropy = cost.mv_cost_type == 0;
-  c.error_per_bit = cost.error_per_bit;
-  c.mvjcost = cost.mvjcost;
-  c.mvcost0 = cost.mvcost[0];
-  c.mvcost1 = cost.mvcost[1];
   // source words of this lane's segments
   uint32_t sv[S::NS];
 #pragma unroll
@@ -366,29 +225,15 @@ __global__ __launch_bounds__(256) void subpel_kernel(const uint8_t* __restrict__
       sv[n] = lo;
     }
   }
-  // setup_center_error: vf at the full-pel start (the bilinear passes with
-  // zero offsets reproduce the plain pixels exactly)
   // start: the job's, or the full-pel search result of the same job index
   const int start_row = fp ? 8 * fp[j].best_row : jb.start_row;
   const int start_col = fp ? 8 * fp[j].best_col : jb.start_col;
+  // setup_center_error: vf at the full-pel start (the bilinear passes with
+  // zero offsets reproduce the plain pixels exactly)
   Best b;
-  b.row = start_row;
-  b.col = start_col;
-  {
-    int sum = 0;
-    uint32_t sse = 0;
-    seg_err<W, H>(c, sv, lane, b.row, b.col, sum, sse);
-    const int ts = (int)wave_total((uint32_t)sum);
-    const uint32_t tq = wave_total(sse);
-    const uint32_t var = tq - (uint32_t)(((int64_t)ts * ts) / (W * H));
-    b.distortion = (int)var;
-    b.sse1 = tq;
-    b.besterr = var + (uint32_t)mv_cost(c, b.row, b.col);
-  }
+  centre_error<W, H>(c, sv, lane, start_row, start_col, start_row, start_col, b);
   if (method == 0) {  // av1_find_best_sub_pixel_tree (mcomp.c:3128-3194), no repeat list
-    const int round = min(3 - forced_stop, 3 - (allow_hp ? 0 : 1));
-    int hstep = 4;
-    for (int it = 0; it < round; ++it, hstep >>= 1) tree_level<W, H>(c, sv, lane, hstep, iters, b);
+    tree_search<W, H>(c, sv, lane, forced_stop, allow_hp, iters, b);
   } else if (forced_stop != 3) {  // FULL_PEL
     int hstep = 4;         // INIT_SUBPEL_STEP_SIZE: half pel
     int cl[5] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX, INT_MAX};
@@ -420,24 +265,9 @@ __global__ __launch_bounds__(256) void subpel_kernel(const uint8_t* __restrict__
     } else {
       two_level<W, H>(c, sv, lane, start_row, start_col, hstep, iters, b);
     }
-    if (forced_stop < 2) {  // below HALF_PEL
-      hstep >>= 1;
-      two_level<W, H>(c, sv, lane, b.row, b.col, hstep, iters, b);
-    }
-    if (allow_hp && forced_stop == 0) {  // EIGHTH_PEL
-      hstep >>= 1;
-      two_level<W, H>(c, sv, lane, b.row, b.col, hstep, iters, b);
-    }
+    pruned_finer<W, H>(c, sv, lane, hstep, forced_stop, allow_hp, iters, b);
   }
-  if (lane == 0) {
-    LavishSubpelResult r;
-    r.best_row = (int16_t)b.row;
-    r.best_col = (int16_t)b.col;
-    r.besterr = b.besterr;
-    r.distortion = b.distortion;
-    r.sse = b.sse1;
-    out[j] = r;
-  }
+  store_record(out, j, lane, b);
 }
 
 template <int W, int H>
@@ -457,16 +287,10 @@ int subpel_batch(const uint8_t* src, int src_stride, const uint8_t* ref, int ref
                  const LavishMvCostParams* cost, const int32_t* cost_lists,
                  LavishSubpelResult* out, hipStream_t s, int search_type = 0) {
   if (njobs <= 0) return 0;
-  if (search_type < 0 || search_type > 3) return -7;
+  if (const int rc = subpel_args_ok(search_type, forced_stop, cost, iters_per_step, method))
+    return rc;
   // USE_2_TAPS_ORIG / USE_2_TAPS: the svf; USE_4_TAPS / USE_8_TAPS: kUpK kind
   const int up_kind = search_type == 2 ? 4 : search_type == 3 ? 0 : -1;
-  if (forced_stop < 0 || forced_stop > 3) return -1;
-  if (cost == nullptr || cost->mv_cost_type < 0 || cost->mv_cost_type > 4) return -2;
-  if (cost->mv_cost_type == 0 &&
-      (cost->mvjcost == nullptr || cost->mvcost[0] == nullptr || cost->mvcost[1] == nullptr))
-    return -2;
-  if (iters_per_step < 1 || iters_per_step > 2) return -4;
-  if (method < 0 || method > 2) return -6;  // SUBPEL_TREE (bilinear) / _PRUNED / _PRUNED_MORE
 #define LAVISH_SP_CASE(W, H)                                                                   \
   if (w == W && h == H) {                                                                      \
     launch<W, H>(src, src_stride, ref, ref_stride, jobs, njobs, fp, method, up_kind,          \
@@ -476,7 +300,7 @@ int subpel_batch(const uint8_t* src, int src_stride, const uint8_t* ref, int ref
   }
   LAVISH_ENCODER_BLOCK_SIZES(LAVISH_SP_CASE)
 #undef LAVISH_SP_CASE
-  return -3;
+  return -3;  // (size_ok(w, h) is false)
 }
 
 LavishMvCostParams l1_cost(int mv_cost_type) {

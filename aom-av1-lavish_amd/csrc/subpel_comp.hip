@@ -25,7 +25,9 @@
 // rows.
 //
 // The bilinear instantiations (UP false) score a level's known candidates
-// together (check_n), as subpel.hip does.  The upsampled ones (UP true; only
+// together through subpel_dev.h's tree (check_n, two_level, tree_level), the
+// one subpel.hip runs; this file supplies the form's error (seg_err) and the
+// candidate's price (cand_cost).  The upsampled ones (UP true; only
 // SUBPEL_TREE reaches them) walk a level one candidate at a time through a
 // single inlined copy of the prediction, so nothing is passed through memory.
 //
@@ -75,20 +77,12 @@ __device__ __forceinline__ void load4_i32(const int32_t* p, int32_t (&o)[4]) {
 }
 __device__ __forceinline__ int byte_of(uint32_t w, int i) { return (w >> (8 * i)) & 0xFF; }
 
-struct Ctx {
+struct Ctx : MvCtx {
   const uint8_t* src;
   const uint8_t* ref;
   int ss, rs;
-  int ref_mv_row, ref_mv_col;
-  int col_min, col_max, row_min, row_max;
-  int lambda;    // mv_err_cost_ L1 lambda (0: MV_COST_NONE)
-  int up_kind;   // kUpK kind of the upsampled error (UP instantiations)
-  bool entropy;
+  int up_kind;    // kUpK kind of the upsampled error (UP instantiations)
   bool estimate;  // candidates priced by estimate_obmc_mvcost
-  int error_per_bit;
-  const int32_t* mvjcost;
-  const int32_t* mvcost0;  // centred at MV_MAX
-  const int32_t* mvcost1;
   const uint8_t* second;  // compact, stride W
   const uint8_t* mask;    // rows ms apart
   int ms, invert;
@@ -110,16 +104,6 @@ __device__ __forceinline__ uint32_t fold_mask(uint32_t m, int invert) {
   return invert ? 0x40404040u - m : m;  // (every byte <= 64: no borrow)
 }
 
-// mv_err_cost_ (mcomp.c:290-323) at a wave-uniform mv
-__device__ __forceinline__ int mv_cost(const Ctx& c, int row, int col) {
-  const int dr = row - c.ref_mv_row, dc = col - c.ref_mv_col;
-  if (c.entropy) {
-    const int joint = (dc != 0) | ((dr != 0) << 1);  // av1_get_mv_joint
-    const int rate = c.mvjcost[joint] + c.mvcost0[dr] + c.mvcost1[dc];
-    return (int)(((int64_t)rate * c.error_per_bit + 8192) >> 14);
-  }
-  return (c.lambda * (abs(dr) + abs(dc))) >> 3;
-}
 // estimate_obmc_mvcost (mcomp.c:3561-3583): the diff through GET_MV_SUBPEL
 // (x 8), int arithmetic, 13-bit rounding; MV_COST_NONE 0 (the L1 types are
 // refused by the entry point).  The reference indexes its tables without a
@@ -131,9 +115,6 @@ __device__ __forceinline__ int obmc_estimate_cost(const Ctx& c, int row, int col
   const int joint = (dc != 0) | ((dr != 0) << 1);
   const uint32_t rate = (uint32_t)(c.mvjcost[joint] + c.mvcost0[dr] + c.mvcost1[dc]);
   return (int)((uint32_t)((int)(rate * (uint32_t)c.error_per_bit + 4096u) >> 13));
-}
-__device__ __forceinline__ bool in_range(const Ctx& c, int row, int col) {
-  return col >= c.col_min && col <= c.col_max && row >= c.row_min && row <= c.row_max;
 }
 
 // segment sg of the prediction v against the job's invariants -- the source,
@@ -225,7 +206,7 @@ __device__ __forceinline__ void bil4(const uint8_t* p, int rs, int f0, int f1, i
 
 // (sum, sse) of the form's difference at mv (row, col) over this lane's
 // segments
-template <int W, int H, int FORM, bool UP>
+template <int W, int H, bool UP = false, int FORM>
 __device__ __forceinline__ void seg_err(const Ctx& c, const Regs<W, H, FORM>& R, int lane, int row,
                                         int col, int& sum, uint32_t& sse) {
   using S = Sp<W, H>;
@@ -293,125 +274,10 @@ __device__ __forceinline__ void seg_err(const Ctx& c, const Regs<W, H, FORM>& R,
   }
 }
 
-// the wave totals of one candidate -> its cost and the strictly-better update
+// a candidate's price: mv_err_cost_, or estimate_obmc_mvcost
 template <int W, int H, int FORM>
-__device__ __forceinline__ uint32_t settle(const Ctx& c, int r, int cl, int sum, uint32_t sse,
-                                           Best& b) {
-  const int ts = (int)wave_total((uint32_t)sum);
-  const uint32_t tq = wave_total(sse);
-  const uint32_t var = tq - (uint32_t)(((int64_t)ts * ts) / (W * H));
-  const int mvc = (FORM == kObmc && c.estimate) ? obmc_estimate_cost(c, r, cl) : mv_cost(c, r, cl);
-  const uint32_t cost = (uint32_t)mvc + var;
-  if (cost < b.besterr) {
-    b.besterr = cost;
-    b.row = r;
-    b.col = cl;
-    b.distortion = (int)var;
-    b.sse1 = tq;
-  }
-  return cost;
-}
-
-// evaluate up to 4 candidates (wave-uniform mvs) together, then the
-// sequential check_better_fast updates; each candidate's cost (INT_MAX when
-// out of range) through cost[]
-template <int W, int H, int FORM, int N>
-__device__ __forceinline__ void check_n(const Ctx& c, const Regs<W, H, FORM>& R, int lane,
-                                        const int (&r)[N], const int (&cl)[N], Best& b,
-                                        uint32_t (&cost)[N]) {
-  int sum[N];
-  uint32_t sse[N];
-  bool ok[N];
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    sum[k] = 0;
-    sse[k] = 0;
-    ok[k] = in_range(c, r[k], cl[k]);
-    if (ok[k]) seg_err<W, H, FORM, false>(c, R, lane, r[k], cl[k], sum[k], sse[k]);
-  }
-#pragma unroll
-  for (int k = 0; k < N; ++k)
-    cost[k] = ok[k] ? settle<W, H, FORM>(c, r[k], cl[k], sum[k], sse[k], b) : 0x7FFFFFFFu;
-}
-
-// two_level_checks_fast (mcomp.c:2675): first_level_check_fast, then with
-// iters_per_step > 1 second_level_check_fast
-template <int W, int H, int FORM>
-__device__ void two_level(const Ctx& c, const Regs<W, H, FORM>& R, int lane, int tr, int tc,
-                          int hstep, int iters, Best& b) {
-  uint32_t cst[4];
-  {
-    const int r[4] = {tr, tr, tr - hstep, tr + hstep};
-    const int cl[4] = {tc - hstep, tc + hstep, tc, tc};
-    check_n<W, H, FORM, 4>(c, R, lane, r, cl, b, cst);
-  }
-  // get_best_diag_step: toward the cheaper of up/down and left/right
-  const int dr = cst[2] <= cst[3] ? -hstep : hstep;
-  const int dc = cst[0] <= cst[1] ? -hstep : hstep;
-  uint32_t d1[1];
-  {
-    const int r[1] = {tr + dr};
-    const int cl[1] = {tc + dc};
-    check_n<W, H, FORM, 1>(c, R, lane, r, cl, b, d1);
-  }
-  if (iters <= 1) return;
-  const int br = b.row, bc = b.col;
-  if (tr != br && tc != bc) {
-    const int r[2] = {br, br + dr};
-    const int cl[2] = {bc + dc, bc};
-    uint32_t d2[2];
-    check_n<W, H, FORM, 2>(c, R, lane, r, cl, b, d2);
-  } else if (tr == br && tc != bc) {
-    const int r[3] = {br + hstep, br - hstep, br - dr};
-    const int cl[3] = {bc + dc, bc + dc, bc};
-    uint32_t d3[3];
-    check_n<W, H, FORM, 3>(c, R, lane, r, cl, b, d3);
-  } else if (tr != br && tc == bc) {
-    const int r[3] = {br + dr, br + dr, br};
-    const int cl[3] = {bc + hstep, bc - hstep, bc - dc};
-    uint32_t d3[3];
-    check_n<W, H, FORM, 3>(c, R, lane, r, cl, b, d3);
-  }
-}
-
-// one tree level with the bilinear error: first_level_check_fast /
-// obmc_first_level_check around the current best, then with iters_per_step
-// > 1 and a moved best second_level_check_v2 / its OBMC twin
-template <int W, int H, int FORM>
-__device__ void tree_level(const Ctx& c, const Regs<W, H, FORM>& R, int lane, int hstep, int iters,
-                           Best& b) {
-  const int tr = b.row, tc = b.col;
-  uint32_t cst[4];
-  {
-    const int r[4] = {tr, tr, tr - hstep, tr + hstep};
-    const int cl[4] = {tc - hstep, tc + hstep, tc, tc};
-    check_n<W, H, FORM, 4>(c, R, lane, r, cl, b, cst);
-  }
-  int dr = cst[2] <= cst[3] ? -hstep : hstep;
-  int dc = cst[0] <= cst[1] ? -hstep : hstep;
-  uint32_t d1[1];
-  {
-    const int r[1] = {tr + dr};
-    const int cl[1] = {tc + dc};
-    check_n<W, H, FORM, 1>(c, R, lane, r, cl, b, d1);
-  }
-  if (iters <= 1) return;
-  const int br = b.row, bc = b.col;
-  if (br == tr && bc == tc) return;
-  if (tr == br) dr = -dr;
-  else if (tc == bc) dc = -dc;
-  const uint32_t before = b.besterr;
-  {
-    const int r[2] = {br + dr, br};
-    const int cl[2] = {bc, bc + dc};
-    uint32_t d2[2];
-    check_n<W, H, FORM, 2>(c, R, lane, r, cl, b, d2);
-  }
-  if (b.besterr != before) {
-    const int r[1] = {br + dr};
-    const int cl[1] = {bc + dc};
-    check_n<W, H, FORM, 1>(c, R, lane, r, cl, b, d1);
-  }
+__device__ __forceinline__ int cand_cost(const Ctx& c, const Regs<W, H, FORM>&, int row, int col) {
+  return (FORM == kObmc && c.estimate) ? obmc_estimate_cost(c, row, col) : mv_cost(c, row, col);
 }
 
 // the same level one candidate at a time (the upsampled error): steps 0-3
@@ -456,8 +322,8 @@ __device__ __forceinline__ void tree_level_seq(const Ctx& c, const Regs<W, H, FO
     if (in_range(c, r, cl)) {
       int sum = 0;
       uint32_t sse = 0;
-      seg_err<W, H, FORM, true>(c, R, lane, r, cl, sum, sse);
-      cost = settle<W, H, FORM>(c, r, cl, sum, sse, b);
+      seg_err<W, H, true>(c, R, lane, r, cl, sum, sse);
+      cost = settle<W, H>(c, R, r, cl, sum, sse, b);
     }
     c0 = s == 0 ? cost : c0;
     c1 = s == 1 ? cost : c1;
@@ -493,21 +359,9 @@ __global__ __launch_bounds__(256) void comp_subpel_kernel(KArgs a, LavishMvCostP
   c.ref = a.ref + jb.ref_off;
   c.ss = a.ss;
   c.rs = a.rs;
-  c.ref_mv_row = jb.ref_mv_row;
-  c.ref_mv_col = jb.ref_mv_col;
-  c.col_min = jb.col_min;
-  c.col_max = jb.col_max;
-  c.row_min = jb.row_min;
-  c.row_max = jb.row_max;
-  // mv_err_cost_ lambdas: SSE_LAMBDA_LOWRES 2, MIDRES 0, HDRES 1; NONE 0
-  c.lambda = cost.mv_cost_type == 1 ? 2 : cost.mv_cost_type == 3 ? 1 : 0;
+  fill_mv_ctx(c, jb, cost);
   c.up_kind = a.up_kind;
-  c.entropy = cost.mv_cost_type == 0;
   c.estimate = a.estimate != 0;
-  c.error_per_bit = cost.error_per_bit;
-  c.mvjcost = cost.mvjcost;
-  c.mvcost0 = cost.mvcost[0];
-  c.mvcost1 = cost.mvcost[1];
   c.second = FORM == kObmc ? nullptr : a.second + jb.second_off;
   c.mask = FORM == kMask ? a.mask + jb.mask_off : nullptr;
   c.ms = a.mask_stride;
@@ -559,52 +413,21 @@ __global__ __launch_bounds__(256) void comp_subpel_kernel(KArgs a, LavishMvCostP
   // full-pel floor (setup_center_error reads get_buf_from_mv's block), or at
   // mv (0, 0) (setup_obmc_center_error); always with the start's mv cost
   Best b;
-  b.row = start_row;
-  b.col = start_col;
   {
     const int er = a.centre == kCentreStart ? start_row : a.centre == kCentreFloor ? start_row & ~7 : 0;
     const int ec = a.centre == kCentreStart ? start_col : a.centre == kCentreFloor ? start_col & ~7 : 0;
-    int sum = 0;
-    uint32_t sse = 0;
-    seg_err<W, H, FORM, UP>(c, R, lane, er, ec, sum, sse);
-    const int ts = (int)wave_total((uint32_t)sum);
-    const uint32_t tq = wave_total(sse);
-    const uint32_t var = tq - (uint32_t)(((int64_t)ts * ts) / (W * H));
-    b.distortion = (int)var;
-    b.sse1 = tq;
-    b.besterr = var + (uint32_t)mv_cost(c, b.row, b.col);
+    centre_error<W, H, UP>(c, R, lane, er, ec, start_row, start_col, b);
   }
-  const int forced_stop = a.forced_stop, iters = a.iters;
-  if (UP || a.method == 0) {  // av1_find_best_sub_pixel_tree / _obmc_sub_pixel_tree_up
-    const int round = min(3 - forced_stop, 3 - (a.allow_hp ? 0 : 1));
+  if constexpr (UP) {  // av1_find_best_sub_pixel_tree / _obmc_sub_pixel_tree_up, any method
+    const int round = tree_rounds(a.forced_stop, a.allow_hp);
     int hstep = 4;  // INIT_SUBPEL_STEP_SIZE: half pel
-    for (int it = 0; it < round; ++it, hstep >>= 1) {
-      if constexpr (UP) tree_level_seq<W, H, FORM>(c, R, lane, hstep, iters, b);
-      else tree_level<W, H, FORM>(c, R, lane, hstep, iters, b);
-    }
-  } else if (forced_stop != 3) {  // the pruned methods without a cost list
-    if constexpr (!UP) {
-      int hstep = 4;
-      two_level<W, H, FORM>(c, R, lane, start_row, start_col, hstep, iters, b);
-      if (forced_stop < 2) {  // below HALF_PEL
-        hstep >>= 1;
-        two_level<W, H, FORM>(c, R, lane, b.row, b.col, hstep, iters, b);
-      }
-      if (a.allow_hp && forced_stop == 0) {  // EIGHTH_PEL
-        hstep >>= 1;
-        two_level<W, H, FORM>(c, R, lane, b.row, b.col, hstep, iters, b);
-      }
-    }
+    for (int it = 0; it < round; ++it, hstep >>= 1)
+      tree_level_seq<W, H>(c, R, lane, hstep, a.iters, b);
+  } else {  // the tree, or the pruned methods without a cost list
+    search_levels<W, H>(c, R, lane, a.method, start_row, start_col, a.forced_stop, a.allow_hp,
+                        a.iters, b);
   }
-  if (lane == 0) {
-    LavishSubpelResult r;
-    r.best_row = (int16_t)b.row;
-    r.best_col = (int16_t)b.col;
-    r.besterr = b.besterr;
-    r.distortion = b.distortion;
-    r.sse = b.sse1;
-    a.out[j] = r;
-  }
+  store_record(a.out, j, lane, b);
 }
 
 template <int W, int H, int FORM>
@@ -615,28 +438,6 @@ void launch(const KArgs& a, bool up, const LavishMvCostParams& cost, hipStream_t
   else
     hipLaunchKernelGGL((comp_subpel_kernel<W, H, FORM, false>), dim3(nwg), dim3(256), 0, s, a,
                        cost);
-}
-
-// the checks both entry points share, in the plain call's order
-int args_ok(int search_type, int forced_stop, const LavishMvCostParams* cost, int iters_per_step,
-            int method) {
-  if (search_type < 0 || search_type > 3) return -7;
-  if (forced_stop < 0 || forced_stop > 3) return -1;
-  if (cost == nullptr || cost->mv_cost_type < 0 || cost->mv_cost_type > 4) return -2;
-  if (cost->mv_cost_type == 0 &&
-      (cost->mvjcost == nullptr || cost->mvcost[0] == nullptr || cost->mvcost[1] == nullptr))
-    return -2;
-  if (iters_per_step < 1 || iters_per_step > 2) return -4;
-  if (method < 0 || method > 2) return -6;
-  return 0;
-}
-
-bool size_ok(int w, int h) {
-#define LAVISH_CSP_SIZE(W, H) \
-  if (w == W && h == H) return true;
-  LAVISH_ENCODER_BLOCK_SIZES(LAVISH_CSP_SIZE)
-#undef LAVISH_CSP_SIZE
-  return false;
 }
 
 int dispatch(int w, int h, int form, bool up, const KArgs& a, const LavishMvCostParams& cost,
@@ -666,8 +467,8 @@ extern "C" int lavish_comp_find_best_sub_pixel_tree_batch(
     int iters_per_step, const LavishMvCostParams* cost, const uint8_t* second_pred,
     const uint8_t* mask, int mask_stride, LavishSubpelResult* out, void* stream) {
   if (njobs <= 0) return 0;
-  if (const int rc = args_ok(subpel_search_type, forced_stop, cost, iters_per_step,
-                             subpel_search_method))
+  if (const int rc = subpel_args_ok(subpel_search_type, forced_stop, cost, iters_per_step,
+                                    subpel_search_method))
     return rc;
   if (!size_ok(w, h)) return -3;
   if (src == nullptr || ref == nullptr || jobs == nullptr || out == nullptr ||
@@ -707,7 +508,7 @@ extern "C" int lavish_obmc_find_best_sub_pixel_tree_batch(
     int allow_hp, int iters_per_step, const LavishMvCostParams* cost, const int32_t* wsrc,
     const int32_t* obmc_mask, LavishSubpelResult* out, void* stream) {
   if (njobs <= 0) return 0;
-  if (const int rc = args_ok(subpel_search_type, forced_stop, cost, iters_per_step, 0))
+  if (const int rc = subpel_args_ok(subpel_search_type, forced_stop, cost, iters_per_step, 0))
     return rc;
   // estimate_obmc_mvcost asserts on the L1 types
   if (subpel_search_type == 0 && cost->mv_cost_type >= 1 && cost->mv_cost_type <= 3) return -2;

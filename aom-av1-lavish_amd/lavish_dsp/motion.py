@@ -552,6 +552,14 @@ def subpel_jobs(width, height, border, bw, bh, fullpel_jobs, fullpel_results, re
     return out
 
 
+def _subpel_out(nj, out, device):
+    import torch
+    if out is None:
+        out = torch.empty(nj * SUBPEL_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=device)
+    assert out.numel() >= nj * SUBPEL_RESULT_DTYPE.itemsize
+    return out
+
+
 def subpel_search_batch(src, ref, w, h, jobs, forced_stop=EIGHTH_PEL, allow_hp=False,
                         iters_per_step=1, mv_cost_type=MV_COST_L1_HDRES, out=None, stream=None):
     """lavish_subpel_search_batch over device planes (as diamond_search_batch)
@@ -561,9 +569,7 @@ def subpel_search_batch(src, ref, w, h, jobs, forced_stop=EIGHTH_PEL, allow_hp=F
     assert src.dtype == torch.uint8 and ref.dtype == torch.uint8
     assert src.is_contiguous() and ref.is_contiguous(), "planes must be C-contiguous"
     nj = jobs.numel() // SUBPEL_JOB_DTYPE.itemsize
-    if out is None:
-        out = torch.empty(nj * SUBPEL_RESULT_DTYPE.itemsize, dtype=torch.uint8,
-                          device=src.device)
+    out = _subpel_out(nj, out, src.device)
     rc = _lib.lavish_subpel_search_batch(_vp(src.data_ptr()), src.stride(0),
                                          _vp(ref.data_ptr()), src.stride(0), w, h,
                                          _vp(jobs.data_ptr()), nj, forced_stop, int(allow_hp),
@@ -583,9 +589,7 @@ def subpel_after_diamond(src, ref, w, h, jobs, fullpel, forced_stop=EIGHTH_PEL, 
     import torch
     nj = jobs.numel() // SUBPEL_JOB_DTYPE.itemsize
     assert fullpel.numel() >= nj * RESULT_DTYPE.itemsize
-    if out is None:
-        out = torch.empty(nj * SUBPEL_RESULT_DTYPE.itemsize, dtype=torch.uint8,
-                          device=src.device)
+    out = _subpel_out(nj, out, src.device)
     rc = _lib.lavish_subpel_search_after_diamond(
         _vp(src.data_ptr()), src.stride(0), _vp(ref.data_ptr()), src.stride(0), w, h,
         _vp(jobs.data_ptr()), _vp(fullpel.data_ptr()), nj, forced_stop, int(allow_hp),
@@ -626,9 +630,7 @@ def find_best_sub_pixel_tree_batch(src, ref, w, h, jobs, cost, method="pruned_mo
         assert fullpel.numel() >= nj * RESULT_DTYPE.itemsize
     if cost_lists is not None:
         assert cost_lists.dtype == torch.int32 and cost_lists.numel() >= 5 * nj
-    if out is None:
-        out = torch.empty(nj * SUBPEL_RESULT_DTYPE.itemsize, dtype=torch.uint8,
-                          device=src.device)
+    out = _subpel_out(nj, out, src.device)
     rc = _lib.lavish_find_best_sub_pixel_tree_batch_ex(
         _vp(src.data_ptr()), src.stride(0), _vp(ref.data_ptr()), src.stride(0), w, h,
         _vp(jobs.data_ptr()), None if fullpel is None else _vp(fullpel.data_ptr()), nj,
@@ -668,14 +670,6 @@ def comp_subpel_jobs(subpel_jobs, second_off, mask_off=0, invert_mask=0):
     out = np.zeros(len(subpel_jobs), COMP_SUBPEL_JOB_DTYPE)
     out["base"] = subpel_jobs
     out["second_off"], out["mask_off"], out["invert_mask"] = second_off, mask_off, invert_mask
-    return out
-
-
-def _subpel_out(nj, out, device):
-    import torch
-    if out is None:
-        out = torch.empty(nj * SUBPEL_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=device)
-    assert out.numel() >= nj * SUBPEL_RESULT_DTYPE.itemsize
     return out
 
 

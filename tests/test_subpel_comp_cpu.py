@@ -2,7 +2,8 @@
 * include/lavish_dsp.h declares, and the library exports, the two batch
   calls; the record sizes and offsets match ctypes and the numpy dtype;
 * every argument the calls refuse is refused with its code before any device
-  work (the pointers are NULL or valid host buffers);
+  work (the pointers are NULL or valid host buffers); the same for the four
+  single-reference calls, whose checks are the same shared validator;
 * tests/_compsubpel_ref.py equals every row of tests/golden/
   fix_subpel_comp.npz (the reference's own results), every field, and with no
   second_pred the CPU oracle of the single-reference search;
@@ -160,6 +161,78 @@ def test_no_jobs_is_a_no_op(which):
     a = Args()
     assert getattr(_lib(), FUNCS[which])(*getattr(a, which)(njobs=0)) == 0
     assert getattr(_lib(), FUNCS[which])(*getattr(a, which)(njobs=-3, w=12, h=12)) == 0
+
+
+# ------------------------------------------------- the plain calls' rejects --
+class PlainArgs(Args):
+    """Argument lists of the four single-reference calls (as Args: NULL or a
+    valid host buffer; they all return before any device work)."""
+
+    def _pre(self, w, h, fullpel):
+        p = self.p
+        return [p, 64, p, 64, w, h, p] + ([] if fullpel is None else [p if fullpel else None])
+
+    def ex(self, w=16, h=16, njobs=1, method=2, stype=0, fstop=0, hp=1, iters=1, cost="ok",
+           fullpel=True):
+        return self._pre(w, h, fullpel) + [njobs, method, stype, fstop, hp, iters,
+                                           self._cost(cost), None, self.p, None]
+
+    def tree(self, w=16, h=16, njobs=1, method=2, fstop=0, hp=1, iters=1, cost="ok",
+             fullpel=True):
+        return self._pre(w, h, fullpel) + [njobs, method, fstop, hp, iters, self._cost(cost),
+                                           None, self.p, None]
+
+    def l1(self, w=16, h=16, njobs=1, fstop=0, hp=1, iters=1, ctype=X.L1, fullpel=None):
+        return self._pre(w, h, fullpel) + [njobs, fstop, hp, iters, ctype, self.p, None]
+
+    def l1fp(self, fullpel=True, **kw):
+        return self.l1(fullpel=fullpel, **kw)
+
+
+PLAIN_FUNCS = dict(ex="lavish_find_best_sub_pixel_tree_batch_ex",
+                   tree="lavish_find_best_sub_pixel_tree_batch",
+                   l1="lavish_subpel_search_batch", l1fp="lavish_subpel_search_after_diamond")
+COSTLY = ("ex", "tree")        # the calls that take a LavishMvCostParams
+BAD = dict(w=12, h=12)         # a bad size: the last refusal of all
+PLAIN_REJECTS = (
+    # one fault each
+    [("ex", dict(stype=v), -7) for v in (-1, 4)] +
+    [(f, dict(fstop=v), -1) for f in PLAIN_FUNCS for v in (-1, 4)] +
+    [(f, dict(cost=c), -2) for f in COSTLY for c in BAD_COSTS] +
+    [(f, dict(ctype=v), -2) for f in ("l1", "l1fp") for v in (0, -1, 5)] +
+    [(f, dict(iters=v), -4) for f in PLAIN_FUNCS for v in (0, 3, -1)] +
+    [(f, dict(method=v), -6) for f in COSTLY for v in (-1, 3, 4)] +
+    [(f, dict(w=w, h=h), -3) for f in PLAIN_FUNCS for w, h in BAD_SIZES] +
+    [("l1fp", dict(fullpel=False), -5)] +
+    # two faults: -7 before -1 before -2 before -4 before -6 before -3
+    [("ex", dict(stype=4, fstop=4), -7), ("ex", dict(stype=-1, **BAD), -7)] +
+    [(f, dict(fstop=4, cost=None), -1) for f in COSTLY] +
+    [(f, dict(fstop=-1, ctype=0), -1) for f in ("l1", "l1fp")] +
+    [(f, dict(cost=None, iters=0), -2) for f in COSTLY] +
+    [(f, dict(cost=(X.ENTROPY, False), method=3), -2) for f in COSTLY] +
+    [(f, dict(ctype=0, iters=3), -2) for f in ("l1", "l1fp")] +
+    [(f, dict(ctype=0, **BAD), -2) for f in ("l1", "l1fp")] +
+    [(f, dict(iters=3, method=3), -4) for f in COSTLY] +
+    [(f, dict(iters=0, **BAD), -4) for f in PLAIN_FUNCS] +
+    [(f, dict(method=-1, **BAD), -6) for f in COSTLY] +
+    # _after_diamond looks at fullpel before anything else, the job count included
+    [("l1fp", dict(fullpel=False, **kw), -5) for kw in (dict(fstop=4), dict(ctype=0), dict(iters=0),
+                                                        BAD, dict(njobs=0), dict(njobs=-3))] +
+    # no jobs: a no-op whatever else is wrong
+    [(f, dict(njobs=n, fstop=4, iters=0, **BAD), 0) for f in PLAIN_FUNCS for n in (0, -3)] +
+    [(f, dict(njobs=0, cost=None, method=3), 0) for f in COSTLY] +
+    [("ex", dict(njobs=0, stype=4), 0)] +
+    [(f, dict(njobs=0, ctype=0), 0) for f in ("l1", "l1fp")])
+
+
+@pytest.mark.parametrize("which,kw,code", PLAIN_REJECTS, ids=lambda v: str(v).replace(" ", ""))
+def test_plain_calls_refuse_bad_arguments_with_their_code(which, kw, code):
+    """The single-reference calls' codes and their precedence: no jobs 0, then
+    search type -7, forced_stop -1, cost -2 (the L1 calls: mv_cost_type 0 too),
+    iters_per_step -4, method -6, size -3; lavish_subpel_search_after_diamond
+    answers a NULL fullpel with -5 first of all."""
+    a = PlainArgs()
+    assert getattr(_lib(), PLAIN_FUNCS[which])(*getattr(a, which)(**kw)) == code
 
 
 # ---------------------------------------------------------------- fixture --
