@@ -7,10 +7,11 @@
 //   av1_obmc_full_pixel_search (:2328-2342): obmc_full_pixel_diamond
 //     (:2293-2326) over obmc_diamond_search_sad (:2235-2291), or
 //     obmc_refining_search_sad (:2190-2233).
-// The wave shape is mcomp_dev.h's: lane group g = lane / 8 takes one
-// candidate site, lane l of the group rows l + 8k, and the keyed minimum
-// (cost << 4 | site) over the groups is the reference's sequential two-stage
-// strict-< scan.  What differs from Search<> is the block SAD: the candidate
+// The walk (diamond_walk) and the wave shape are
+// mcomp_dev.h's: lane group g = lane / 8 takes one candidate site, lane l of
+// the group rows l + 8k, and the keyed minimum (cost << 4 | site) over the
+// groups is the reference's sequential two-stage strict-< scan.  What this
+// file adds is the SAD source CompSearch<> and the refinements: the candidate
 // is first combined with a job-invariant block -- the rounded average with
 // second_pred (sdaf), the mask blend with it (msdf), or the weighted OBMC
 // difference against wsrc (osdf).  Up to 32x32 those invariants are staged
@@ -239,20 +240,12 @@ struct CompSearch {
         }
       }
     } else {
-      // rows in 32-byte chunks, not unrolled (keeps code and VGPRs small)
-      constexpr int CH = DW < 8 ? DW : 8;
-#pragma unroll 1
-      for (int k = 0; k < RPL; ++k) {
-        const int row = l + 8 * k;
-        const uint8_t* rp = base + (int64_t)row * c.rs;
-#pragma unroll 1
-        for (int x = 0; x < DW; x += CH) {
-          uint32_t rw[CH];
-          load_row<CH>(rp + 4 * x, rw);
+      acc = chunk_rows<DW, RPL, 1>(
+          base, c.rs, l, [&](const uint32_t (&rw)[kChunk<DW>], int y, int x, uint32_t a) {
 #pragma unroll
-          for (int i = 0; i < CH; ++i) acc = word_mem(c, rw[i], row, x + i, acc);
-        }
-      }
+            for (int i = 0; i < kChunk<DW>; ++i) a = word_mem(c, rw[i], y, x + i, a);
+            return a;
+          });
     }
     return group_sum8(acc);
   }
@@ -261,99 +254,31 @@ struct CompSearch {
   // whole wave walks the block one word per lane, everything from global
   // memory (once per run)
   __device__ int var_cost_at(const Ctx& c, int lane, int row, int col) const {
-    int sum = 0;
-    uint32_t sse = 0;
-    const uint8_t* rb = c.ref + (int64_t)row * c.rs + col;
-    for (int i = lane; i < H * DW; i += 64) {
-      const int y = i / DW, x = i - y * DW;
-      uint32_t b[1];
-      load_row<1>(rb + (int64_t)y * c.rs + 4 * x, b);
-      if constexpr (FORM == kObmc) {
-        int32_t w4[4], m4[4];
-        load4_i32(iv.wsrc + 4 * i, w4);
-        load4_i32(iv.omask + 4 * i, m4);
+    return var_walk<W, H>(
+        c, lane, row, col, nullptr,
+        [&](const uint8_t* rp, int i, int y, int x, int& sum, uint32_t& sse) {
+          uint32_t b[1];
+          load_row<1>(rp, b);
+          if constexpr (FORM == kObmc) {
+            int32_t w4[4], m4[4];
+            load4_i32(iv.wsrc + 4 * i, w4);
+            load4_i32(iv.omask + 4 * i, m4);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          // ROUND_POWER_OF_TWO_SIGNED(wsrc - pre * mask, 12)
-          const int v = w4[j] - __mul24((int)byte_of(b[0], j), m4[j]);
-          const int rnd = (abs(v) + 2048) >> 12, d = v < 0 ? -rnd : rnd;
-          sum += d;
-          sse += (uint32_t)(d * d);
-        }
-      } else {
-        uint32_t a[1];
-        load_row<1>(c.src + (int64_t)y * c.ss + 4 * x, a);
-        var_acc(a[0], pred_mem(b[0], y, x), sum, sse);
-      }
-    }
-    return var_finish<W, H>(c, sum, sse, row, col);
+            for (int j = 0; j < 4; ++j) {
+              // ROUND_POWER_OF_TWO_SIGNED(wsrc - pre * mask, 12)
+              const int v = w4[j] - __mul24((int)byte_of(b[0], j), m4[j]);
+              const int rnd = (abs(v) + 2048) >> 12, d = v < 0 ? -rnd : rnd;
+              sum += d;
+              sse += (uint32_t)(d * d);
+            }
+          } else {
+            uint32_t a[1];
+            load_row<1>(c.src + (int64_t)y * c.ss + 4 * x, a);
+            var_acc(a[0], pred_mem(b[0], y, x), sum, sse);
+          }
+        });
   }
 };
-
-__device__ __forceinline__ int walk_radius(int method, int step) {
-  return method == kDiamond ? 1 << step : nstep_radius(step);
-}
-
-// One diamond_search_sad run (its second_pred branch, or
-// obmc_diamond_search_sad when OB) from the clamped start (srow, scol),
-// whose cost c0 the caller read once.  sec_r / sec_c: tmp_second_best_mv.
-template <bool OB, class S_t>
-__device__ __forceinline__ void walk(const S_t& S, const Ctx& c, int lane, int method, int srow,
-                                     int scol, uint32_t c0, int search_step, int& brow,
-                                     int& bcol, int& num00, int& steps, int& sec_r, int& sec_c) {
-  const int g = lane >> 3;
-  int row = srow, col = scol, off_center = 0, center = 0;
-  uint32_t best = c0;
-  // one round: site (first + g) of the step at radius rad / tangent tan
-  auto round = [&](int rad, int tan, int first, int cnt) -> uint32_t {
-    const int i = first + g;  // 0-based site index (site i + 1)
-    int dr, dc;
-    nstep_site(i, rad, tan, dr, dc);
-    const int r = row + dr, cc = col + dc;
-    const bool valid = g < cnt && cc >= c.col_min && cc <= c.col_max && r >= c.row_min &&
-                       r <= c.row_max;
-    const MvRate mr = mvsad_rate(c, r, cc);
-    const uint32_t mine = S.group_sad(c, r, cc, valid, row, col);
-    const uint32_t mvs = mvsad_finish(c, mr, r, cc);
-    return groups_min((((mine + mvs) << 4) | (uint32_t)i) | (valid ? 0u : ~0u));
-  };
-  for (int step = method_steps(method) - search_step - 1; step >= 0; --step) {
-    const int rad = walk_radius(method, step);
-    const int npts = (method == kNstep && rad > 5) ? 12 : 8;
-    const int tan = npts == 8 ? rad : nstep_tan(step);
-    uint32_t kmin = round(rad, tan, 0, 8);
-    if (npts == 12) kmin = min(kmin, round(rad, tan, 8, 4));
-    ++steps;
-    bool moved = false;
-    if (kmin < (best << 4)) {
-      best = kmin >> 4;
-      int dr, dc;
-      nstep_site((int)(kmin & 15), rad, tan, dr, dc);
-      sec_r = row;
-      sec_c = col;
-      row += dr;
-      col += dc;
-      off_center = 1;
-      moved = true;
-    }
-    if constexpr (OB) {
-      // no equal-radius skip; a centre step is one that did not move while
-      // the walk stands on its start, wherever it has been
-      if (!moved && row == srow && col == scol) ++center;
-    } else {
-      if (!off_center) ++center;
-      if (!moved && step > 2) {  // UPDATE_SEARCH_STEP: skip the equal radii
-        while (step > 2 && walk_radius(method, step - 1) == rad) {
-          ++center;
-          --step;
-        }
-      }
-    }
-  }
-  brow = row;
-  bcol = col;
-  num00 = center;
-}
 
 // neighbour j of av1_refining_search_8p_c: (-1,0) (0,-1) (0,1) (1,0) (-1,-1)
 // (1,-1) (-1,1) (1,1); the first four are obmc_refining_search_sad's.
@@ -446,7 +371,8 @@ __global__ __launch_bounds__(64 * kDkWaves) void comp_kernel(
     // full_pixel_diamond / obmc_full_pixel_diamond
     constexpr bool OB = FORM == kObmc;
     int n, num00 = 0;
-    walk<OB>(S, c, lane, method, srow, scol, c0, step_param, br, bc, n, steps, sec_r, sec_c);
+    diamond_walk<true, OB>(S, c, lane, method, srow, scol, c0, step_param, br, bc, n, steps,
+                           &sec_r, &sec_c);
     sme = S.var_cost_at(c, lane, br, bc);
     const int further = method_steps(method) - 1 - step_param;
     while (n < further) {
@@ -456,8 +382,8 @@ __global__ __launch_bounds__(64 * kDkWaves) void comp_kernel(
         continue;
       }
       int tr, tc;
-      walk<OB>(S, c, lane, method, srow, scol, c0, step_param + n, tr, tc, num00, steps, sec_r,
-               sec_c);
+      diamond_walk<true, OB>(S, c, lane, method, srow, scol, c0, step_param + n, tr, tc, num00,
+                             steps, &sec_r, &sec_c);
       const int t = S.var_cost_at(c, lane, tr, tc);
       if (t < sme) {
         sme = t;

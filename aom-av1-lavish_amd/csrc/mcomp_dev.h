@@ -24,6 +24,14 @@
 // is lower, since the mv cost is >= 0), so the walk and every tie are the
 // reference's.  The source block stays in VGPRs for the whole search;
 // reference pixels come from L2 / MALL (a 1080p padded reference is ~2.5 MB).
+//
+// diamond_search_sad exists twice: Search::diamond (plain DIAMOND, radii <= 8
+// from an LDS window) and diamond_walk, a template over the SAD source (plain
+// NSTEP / NSTEP_8PT here, every compound / OBMC method in mcomp_comp.hip).
+// The uncached chunk loop (chunk_rows) and the whole-wave variance walk
+// (var_walk) exist once; the run loop of full_pixel_diamond is written per
+// kernel (full_pixel_diamond here, comp_kernel): shared, the compound
+// searches ran 1-2% slower.
 #pragma once
 #include <type_traits>
 
@@ -246,21 +254,55 @@ __device__ __forceinline__ int var_finish(const Ctx& c, int sum, uint32_t sse, i
   return (int)var + mv_cost(c, row, col);
 }
 
-// the whole wave walks the W*H pixels one word per lane, from global memory
-template <int W, int H>
-__device__ int var_cost(const Ctx& c, int lane, int row, int col, uint32_t* vout = nullptr) {
+// the whole wave walks the W*H pixels one word per lane, from global memory:
+// word(rp, i, y, x, sum, sse) accumulates word i (x of row y, the reference's
+// at rp) -- plain here, the compound and OBMC forms in mcomp_comp.hip
+template <int W, int H, class F>
+__device__ __forceinline__ int var_walk(const Ctx& c, int lane, int row, int col, uint32_t* vout,
+                                        F&& word) {
   constexpr int DW = W / 4;
   int sum = 0;
   uint32_t sse = 0;
   const uint8_t* rb = c.ref + (int64_t)row * c.rs + col;
   for (int i = lane; i < H * DW; i += 64) {
     const int y = i / DW, x = i - y * DW;
-    uint32_t a[1], b[1];
-    load_row<1>(c.src + (int64_t)y * c.ss + 4 * x, a);
-    load_row<1>(rb + (int64_t)y * c.rs + 4 * x, b);
-    var_acc(a[0], b[0], sum, sse);
+    word(rb + (int64_t)y * c.rs + 4 * x, i, y, x, sum, sse);
   }
   return var_finish<W, H>(c, sum, sse, row, col, vout);
+}
+template <int W, int H>
+__device__ int var_cost(const Ctx& c, int lane, int row, int col, uint32_t* vout = nullptr) {
+  return var_walk<W, H>(c, lane, row, col, vout,
+                        [&](const uint8_t* rp, int, int y, int x, int& sum, uint32_t& sse) {
+                          uint32_t a[1], b[1];
+                          load_row<1>(c.src + (int64_t)y * c.ss + 4 * x, a);
+                          load_row<1>(rp, b);
+                          var_acc(a[0], b[0], sum, sse);
+                        });
+}
+
+// Group-partial SAD of a block too large for VGPRs: lane l's rows
+// (l + 8k) * YS of the candidate at base, in 32-byte chunks, not unrolled
+// (keeps code and VGPRs small).  comb(r, y, x, acc) adds the chunk's
+// candidate words r (row y, from word x on) against what the source re-reads
+// there.
+template <int DW>
+constexpr int kChunk = DW < 8 ? DW : 8;
+template <int DW, int RPL, int YS, class F>
+__device__ __forceinline__ uint32_t chunk_rows(const uint8_t* base, int rs, int l, F&& comb) {
+  uint32_t acc = 0;
+#pragma unroll 1
+  for (int k = 0; k < RPL; ++k) {
+    const int y = (l + 8 * k) * YS;
+    const uint8_t* rp = base + (int64_t)y * rs;
+#pragma unroll 1
+    for (int x = 0; x < DW; x += kChunk<DW>) {
+      uint32_t r[kChunk<DW>];
+      load_row<kChunk<DW>>(rp + 4 * x, r);
+      acc = comb(r, y, x, acc);
+    }
+  }
+  return acc;
 }
 
 // sdf and sdsf (aom_sad / aom_sad_skip) at a full-pel mv in one pass: the
@@ -349,7 +391,7 @@ __device__ __forceinline__ int site_dc(int i) { return ((0x2885 >> (2 * i)) & 3)
 // av1_init_motion_compensation_nstep (mcomp.c:452-494): radius of step st
 // (1, 2, 3, 5, 8, 12, 18, 27, 41, 62, 93, 140, then 210: the radius grows
 // to max((int)(1.5 r + 0.5), r + 1) after each of the first 12 stages) and
-// the step count (NSTEP 15, NSTEP_8PT 16)
+// the step count (method_steps: NSTEP 15, NSTEP_8PT 16)
 __device__ __forceinline__ int nstep_radius(int st) {
   constexpr uint32_t kLo[4] = {0x05030201u, 0x1b120c08u, 0x8c5d3e29u, 0xd2d2d2d2u};
   const int w = st >> 2, b = (st & 3) * 8;
@@ -363,7 +405,21 @@ __device__ __forceinline__ int nstep_tan(int st) {
   const uint32_t v = w == 1 ? 0x0b070403u : w == 2 ? 0x39261910u : w == 3 ? 0x56565656u : 0u;
   return (int)((v >> b) & 0xFF);
 }
-__device__ __forceinline__ int nstep_steps(int level) { return level > 0 ? 16 : 15; }
+// search_method values of SEARCH_METHODS (av1/encoder/mcomp_structs.h:56-86)
+enum {
+  kDiamond = 0, kNstep = 1, kNstep8 = 2, kHex = 4, kBigdia = 5, kSquare = 6, kFastHex = 7,
+  kFastDiamond = 8, kFastBigdia = 9, kVfastDiamond = 10
+};
+// the diamond_search_sad walks (full_pixel_diamond); the others are pattern searches
+__host__ __device__ __forceinline__ bool diamond_method(int m) {
+  return m == kDiamond || m == kNstep || m == kNstep8;
+}
+__host__ __device__ __forceinline__ int method_steps(int m) {
+  return m == kNstep ? 15 : m == kNstep8 ? 16 : kMaxSteps;
+}
+__device__ __forceinline__ int walk_radius(int method, int step) {
+  return method == kDiamond ? 1 << step : nstep_radius(step);
+}
 // site i + 1 (i = 0..11) at radius r, tangent t: (-r,0) (r,0) (0,-r) (0,r)
 // (-r,-t) (r,t) (-t,r) (t,-r) (-r,t) (r,-t) (t,r) (-t,-r)
 __device__ __forceinline__ void nstep_site(int i, int r, int t, int& dr, int& dc) {
@@ -403,11 +459,6 @@ struct Search {
   uint32_t sv[kVarWin ? VN : 1];
   bool inwin;               // the last diamond() ended inside its window
   bool wfilled;             // win holds the window at (wr0, wc0)
-  // every diamond_search_sad run of a full_pixel_diamond starts at the same
-  // clamped start_mv: its SAD is read once
-  bool have_c0;
-  int c0row, c0col;
-  uint32_t c0sad;
   int l;  // lane within the group
   lds_u32 win;              // this wave's window (WN::SIZE dwords), or null
   int wr0, wc0;             // window origin (mv units: block top-left at ref + wr0*rs + wc0)
@@ -418,7 +469,6 @@ struct Search {
     win = w;
     inwin = false;
     wfilled = false;
-    have_c0 = false;
     if constexpr (kVarWin) {
 #pragma unroll
       for (int v = 0; v < VN; ++v) {
@@ -477,22 +527,15 @@ struct Search {
         }
       }
     } else {
-      // rows in 32-byte chunks, not unrolled (keeps code and VGPRs small)
-      constexpr int CH = G::DW < 8 ? G::DW : 8;
-#pragma unroll 1
-      for (int k = 0; k < G::RPL; ++k) {
-        const int row = l + 8 * k;
-        const uint8_t* rp = c.ref + off + (int64_t)row * G::YS * c.rs;
-        const uint8_t* sp = c.src + (int64_t)row * G::YS * c.ss;
-#pragma unroll 1
-        for (int x = 0; x < G::DW; x += CH) {
-          uint32_t r[CH], q[CH];
-          load_row<CH>(rp + 4 * x, r);
-          load_row<CH>(sp + 4 * x, q);
+      constexpr int CH = kChunk<G::DW>;
+      acc = chunk_rows<G::DW, G::RPL, G::YS>(
+          c.ref + off, c.rs, l, [&](const uint32_t (&r)[CH], int y, int x, uint32_t a) {
+            uint32_t q[CH];
+            load_row<CH>(c.src + (int64_t)y * c.ss + 4 * x, q);
 #pragma unroll
-          for (int i = 0; i < CH; ++i) acc = sad4(q[i], r[i], acc);
-        }
-      }
+            for (int i = 0; i < CH; ++i) a = sad4(q[i], r[i], a);
+            return a;
+          });
     }
     acc = group_sum8(acc);
     return SKIP ? 2 * acc : acc;
@@ -607,23 +650,17 @@ struct Search {
     return var_cost<W, H>(c, lane, row, col, vout);
   }
 
-  // diamond_search_sad (no second_pred): returns bestsad
-  __device__ __forceinline__ uint32_t diamond(const Ctx& c, int lane, int srow, int scol,
-                                              int search_step, int& brow, int& bcol,
-                                              int& num00, int& steps) {
+  // diamond_search_sad (no second_pred) over the DIAMOND sites from the
+  // clamped start (srow, scol), whose SAD sad0 the caller read once: the form
+  // of diamond_walk (below) that serves radii <= 8 from the LDS window
+  __device__ __forceinline__ void diamond(const Ctx& c, int lane, int srow, int scol,
+                                          uint32_t sad0, int search_step, int& brow, int& bcol,
+                                          int& num00, int& steps) {
     const int g = lane >> 3;
     // site g + 1 of av1_init_dsmotion_compensation (row, col) in units of radius
     const int sdr = site_dr(g), sdc = site_dc(g);
-    srow = min(max(srow, c.row_min), c.row_max);
-    scol = min(max(scol, c.col_min), c.col_max);
     int row = srow, col = scol, off_center = 0, center = 0;
-    if (!have_c0 || c0row != srow || c0col != scol) {
-      c0sad = rdlane(group_sad(c, srow, scol), 0);
-      have_c0 = true;
-      c0row = srow;
-      c0col = scol;
-    }
-    uint32_t best = mvsad_cost(c, row, col) + c0sad;
+    uint32_t best = sad0 + mvsad_cost(c, row, col);
     const int tot = kMaxSteps - search_step;
     inwin = false;
     // one step: the 8 sites at radius rad around (row, col), straight-line
@@ -674,77 +711,90 @@ struct Search {
     brow = row;
     bcol = col;
     num00 = center;
-    return best;
   }
+};
 
-  // diamond_search_sad over the site configuration of
-  // av1_init_motion_compensation_nstep (mcomp.c:452-494; level 0: NSTEP, 15
-  // steps, 12 points once the radius passes 5; level 1: NSTEP_8PT, 16 steps
-  // of 8 points), candidates from global memory.  12 points take two rounds
-  // (sites 1..8, then 9..12); key = cost * 16 + site index, so the minimum
-  // over both rounds is the reference's sequential strict-< scan.  The steps
-  // of an equal radius below an unmoved step are skipped and counted as
-  // centre steps (UPDATE_SEARCH_STEP, mcomp.c:1334-1341).
-  __device__ __forceinline__ uint32_t nstep_diamond(const Ctx& c, int lane, int level, int srow,
-                                                    int scol, int search_step, int& brow,
-                                                    int& bcol, int& num00, int& steps) {
-    const int g = lane >> 3;
-    srow = min(max(srow, c.row_min), c.row_max);
-    scol = min(max(scol, c.col_min), c.col_max);
-    int row = srow, col = scol, off_center = 0, center = 0;
-    if (!have_c0 || c0row != srow || c0col != scol) {
-      c0sad = rdlane(group_sad(c, srow, scol), 0);
-      have_c0 = true;
-      c0row = srow;
-      c0col = scol;
-    }
-    uint32_t best = mvsad_cost(c, row, col) + c0sad;
-    const int tot = nstep_steps(level) - search_step;
-    inwin = false;
-    // one round: site (first + g) of the step at radius rad / tangent tan
-    auto round = [&](int rad, int tan, int first, int cnt) -> uint32_t {
-      const int i = first + g;  // 0-based site index (site i + 1)
+// One diamond_search_sad run (mcomp.c:1318-1477; obmc_diamond_search_sad
+// :2235-2291 when OB) over the SAD source S from the clamped start
+// (srow, scol), whose cost c0 the caller formed from the SAD it read once.  Sites of
+// av1_init_dsmotion_compensation (DIAMOND) or
+// av1_init_motion_compensation_nstep (:452-494; NSTEP: 15 steps, 12 points
+// once the radius passes 5; NSTEP_8PT: 16 steps of 8 points), all from
+// nstep_site (tangent = radius on 8-point steps), candidates from global
+// memory.  12 points take two rounds (sites 1..8, then 9..12); key = cost *
+// 16 + site index (costs < 2^26 for blocks <= 128x128), so the minimum over
+// both rounds is the reference's sequential strict-< scan.  The steps of an
+// equal radius below an unmoved step are skipped and counted as centre steps
+// (UPDATE_SEARCH_STEP, :1334-1341).  SEC: tmp_second_best_mv into sec_r /
+// sec_c.
+template <bool SEC, bool OB, class S_t>
+__device__ __forceinline__ void diamond_walk(const S_t& S, const Ctx& c, int lane, int method,
+                                             int srow, int scol, uint32_t c0, int search_step,
+                                             int& brow, int& bcol, int& num00, int& steps,
+                                             int* sec_r = nullptr, int* sec_c = nullptr) {
+  const int g = lane >> 3;
+  int row = srow, col = scol, off_center = 0, center = 0;
+  uint32_t best = c0;
+  // one round: site (first + g) of the step at radius rad / tangent tan
+  auto round = [&](int rad, int tan, int first, int cnt) -> uint32_t {
+    const int i = first + g;  // 0-based site index (site i + 1)
+    int dr, dc;
+    nstep_site(i, rad, tan, dr, dc);
+    const int r = row + dr, cc = col + dc;
+    const bool valid = g < cnt && cc >= c.col_min && cc <= c.col_max && r >= c.row_min &&
+                       r <= c.row_max;
+    const MvRate mr = mvsad_rate(c, r, cc);
+    const uint32_t mine = S.group_sad(c, r, cc, valid, row, col);
+    const uint32_t mvs = mvsad_finish(c, mr, r, cc);
+    return groups_min((((mine + mvs) << 4) | (uint32_t)i) | (valid ? 0u : ~0u));
+  };
+  for (int step = method_steps(method) - search_step - 1; step >= 0; --step) {
+    const int rad = walk_radius(method, step);
+    // Two conditions of this loop are written twice, per caller, for the code
+    // they compile to and nothing else: the plain kernels need the first form
+    // (the other order of the skip test doubles their spilled SGPRs, the other
+    // npts form adds scratch at 64x16), and with the second form comp_kernel
+    // compiles to the code it had with a walk of its own, which the first
+    // form makes 1-3% slower on the average, mask and refinement calls
+    const bool twelve = SEC ? (method == kNstep && rad > 5) : !(rad <= 5 || method != kNstep);
+    const int npts = twelve ? 12 : 8;
+    const int tan = npts == 8 ? rad : nstep_tan(step);
+    uint32_t kmin = round(rad, tan, 0, 8);
+    if (npts == 12) kmin = min(kmin, round(rad, tan, 8, 4));
+    ++steps;
+    bool moved = false;
+    if (kmin < (best << 4)) {
+      best = kmin >> 4;
       int dr, dc;
-      nstep_site(i, rad, tan, dr, dc);
-      const int r = row + dr, cc = col + dc;
-      const bool valid = g < cnt && cc >= c.col_min && cc <= c.col_max && r >= c.row_min &&
-                         r <= c.row_max;
-      const MvRate mr = mvsad_rate(c, r, cc);
-      const uint32_t mine = group_sad(c, r, cc, valid, row, col);
-      const uint32_t mvs = mvsad_finish(c, mr, r, cc);
-      return groups_min((((mine + mvs) << 4) | (uint32_t)i) | (valid ? 0u : ~0u));
-    };
-    for (int step = tot - 1; step >= 0; --step) {
-      const int rad = nstep_radius(step);
-      const int npts = (rad <= 5 || level > 0) ? 8 : 12;
-      const int tan = npts == 8 ? rad : nstep_tan(step);
-      uint32_t kmin = round(rad, tan, 0, 8);
-      if (npts == 12) kmin = min(kmin, round(rad, tan, 8, 4));
-      ++steps;
-      bool moved = false;
-      if (kmin < (best << 4)) {
-        best = kmin >> 4;
-        int dr, dc;
-        nstep_site((int)(kmin & 15), rad, tan, dr, dc);
-        row += dr;
-        col += dc;
-        off_center = 1;
-        moved = true;
+      nstep_site((int)(kmin & 15), rad, tan, dr, dc);
+      if constexpr (SEC) {
+        *sec_r = row;
+        *sec_c = col;
       }
+      row += dr;
+      col += dc;
+      off_center = 1;
+      moved = true;
+    }
+    if constexpr (OB) {
+      // no equal-radius skip; a centre step is one that did not move while
+      // the walk stands on its start, wherever it has been
+      if (!moved && row == srow && col == scol) ++center;
+    } else {
       if (!off_center) ++center;
-      if (!moved && step > 2) {
-        while (nstep_radius(step - 1) == rad && step > 2) {
+      if (!moved && step > 2) {  // UPDATE_SEARCH_STEP: skip the equal radii
+        while (SEC ? (step > 2 && walk_radius(method, step - 1) == rad)
+                   : (walk_radius(method, step - 1) == rad && step > 2)) {
           ++center;
           --step;
         }
       }
     }
-    brow = row;
-    bcol = col;
-    num00 = center;
-    return best;
   }
-};
+  brow = row;
+  bcol = col;
+  num00 = center;
+}
 
 // cl[i] = v for a wave-uniform but dynamic i, without a private-array index
 __device__ __forceinline__ void set_cl(int (&cl)[5], int i, int v) {
@@ -779,24 +829,30 @@ __device__ void int_sad_list(const S_t& S, const Ctx& c, int lane, int br, int b
   if (cl[4] != INT_MAX) cl[4] += (int)mvsad_cost(c, br - 1, bc);
 }
 
-// full_pixel_diamond (mcomp.c:1479-1526)
-// level -1: DIAMOND (av1_init_dsmotion_compensation); 0 / 1: NSTEP /
-// NSTEP_8PT (no LDS window: their radii do not shrink by halves)
+// full_pixel_diamond (mcomp.c:1479-1526) of DIAMOND / NSTEP / NSTEP_8PT; the
+// LDS window serves DIAMOND only (the others' radii do not shrink by halves).
+// Every run starts at the same clamped start_mv: its SAD is read once
 template <int W, int H, bool SKIP, bool TL>
 __device__ int full_pixel_diamond(const Ctx& c, int lane, int srow, int scol, int step_param,
                                   int& brow, int& bcol, int& steps, int& searches, lds_u32 win,
-                                  bool want_cl, int (&cl)[5], int level = -1) {
+                                  bool want_cl, int (&cl)[5], int method = kDiamond) {
   Search<W, H, SKIP, true, TL> S;
-  S.load_src(c, lane, level < 0 ? win : nullptr);
+  S.load_src(c, lane, method == kDiamond ? win : nullptr);
+  srow = min(max(srow, c.row_min), c.row_max);
+  scol = min(max(scol, c.col_min), c.col_max);
+  const uint32_t sad0 = rdlane(S.group_sad(c, srow, scol), 0);
   int n, num00 = 0;
   auto run = [&](int sp, int& r, int& cc, int& n00) {
-    if (level < 0) S.diamond(c, lane, srow, scol, sp, r, cc, n00, steps);
-    else S.nstep_diamond(c, lane, level, srow, scol, sp, r, cc, n00, steps);
+    if (method == kDiamond)
+      S.diamond(c, lane, srow, scol, sad0, sp, r, cc, n00, steps);
+    else
+      diamond_walk<false, false>(S, c, lane, method, srow, scol,
+                                 sad0 + mvsad_cost(c, srow, scol), sp, r, cc, n00, steps);
   };
   run(step_param, brow, bcol, n);
   ++searches;
   int bestsme = S.var_cost_at(c, lane, brow, bcol);
-  const int further = (level < 0 ? kMaxSteps : nstep_steps(level)) - 1 - step_param;
+  const int further = method_steps(method) - 1 - step_param;
   while (n < further) {
     ++n;
     int tr, tc;
@@ -1140,19 +1196,6 @@ __device__ int pattern(const Ctx& c, int lane, int srow, int scol, int search_st
 #endif
 constexpr int kDkWaves = LAVISH_DK_WAVES;
 
-// search_method values of SEARCH_METHODS (av1/encoder/mcomp_structs.h:56-86)
-enum {
-  kDiamond = 0, kNstep = 1, kNstep8 = 2, kHex = 4, kBigdia = 5, kSquare = 6, kFastHex = 7,
-  kFastDiamond = 8, kFastBigdia = 9, kVfastDiamond = 10
-};
-// the diamond_search_sad walks (full_pixel_diamond); the others are pattern searches
-__host__ __device__ __forceinline__ bool diamond_method(int m) {
-  return m == kDiamond || m == kNstep || m == kNstep8;
-}
-__host__ __device__ __forceinline__ int method_steps(int m) {
-  return m == kNstep ? 15 : m == kNstep8 ? 16 : kMaxSteps;
-}
-
 // search context of one job: its buffers, FullMvLimits, ref_mv and mv costs
 __device__ __forceinline__ Ctx job_ctx(const uint8_t* src, int ss, const uint8_t* ref, int rs,
                                        const Job& jb, const LavishMvCostParams& cost) {
@@ -1196,8 +1239,7 @@ __device__ __forceinline__ int job_search(const Ctx& c, int lane, int start_row,
     constexpr bool SK = decltype(skip_tag)::value;
     if constexpr (!PAT) {
       return full_pixel_diamond<W, H, SK, TL>(c, lane, start_row, start_col, step_param, br, bc,
-                                              steps, searches, win, want_cl, cl,
-                                              method == kNstep ? 0 : method == kNstep8 ? 1 : -1);
+                                              steps, searches, win, want_cl, cl, method);
     } else {
       // bigdia / hex / square (do_init 1), fast_dia / vfast_dia / fast_bigdia
       // / fast_hex (do_init 0) (mcomp.c:1258-1316)

@@ -353,8 +353,10 @@ __global__ __launch_bounds__(128) void tpl_mv_kernel(TplMvArgs a) {
       int br, bc, steps = 0, searches = 0;
       uint32_t var = 0;
       const lds_u32 win = (lds_u32)win_s;
+      // (the host launches the !PAT kernel for DIAMOND only: no NSTEP walk in it)
       const int sme = job_search<W, H, PAT, false, PAT>(ci, lane, rawpel(mr), rawpel(mc),
-                                                        a.step_param, a.skip, a.method, win,
+                                                        a.step_param, a.skip,
+                                                        PAT ? a.method : (int)kDiamond, win,
                                                         want_cl, cl, br, bc, steps, searches,
                                                         &var, false);
       // find_fractional_mv_step at FULL_PEL: setup_center_error, the plain

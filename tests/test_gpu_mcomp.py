@@ -150,3 +150,52 @@ def test_bigdia_cost_types_and_skip(M, planes, cost):
 def test_bigdia_edges(M, planes):
     _run(M, planes, 16, 16, step_param=6, start=(-900, 700), method="bigdia")
     _run(M, planes, 32, 32, step_param=8, start=(300, -300), ref_mv=(-40, 33), method="bigdia")
+
+
+# ---- NSTEP / NSTEP_8PT (diamond_search_sad over the nstep sites) ----
+
+# (bw, bh, use_downsampled_sad): one row per lane (4x4, 8x8), 16x8, the largest
+# block whose source stays in VGPRs (64x16), the smallest that re-reads it
+# through L2 (32x64); the downsampled SAD where it applies
+NSTEP_SHAPES = [(4, 4, False), (8, 8, False), (16, 8, False), (64, 16, False), (32, 64, False),
+                (16, 16, True), (32, 64, True)]
+NSTEP_JOBS = 320  # per batch: a few seconds with the oracle
+
+
+def nstep_jobs(M, planes, bw, bh):
+    """Starts in the interior and starts clamped onto a limit, every
+    reference, sub-sampled evenly over the frame."""
+    W, H, src, refs = planes
+    sets = [M.frame_jobs(W, H, src.shape[1], BORDER, src.size, bw, bh, refs.shape[0], (13, -21),
+                         start) for start in ((2, -3), (-900, 700), (300, -300))]
+    return np.concatenate([j[::max(1, 3 * len(j) // NSTEP_JOBS)] for j in sets])
+
+
+@pytest.mark.parametrize("step_param", [0, 13])
+@pytest.mark.parametrize("bw,bh,skip", NSTEP_SHAPES)
+@pytest.mark.parametrize("method", ["nstep", "nstep_8pt"])
+def test_nstep_steps_and_cost_lists(M, planes, method, bw, bh, skip, step_param):
+    """Every record field and the cost lists of the plain NSTEP / NSTEP_8PT
+    search against the oracle: `steps` is what a walk can get wrong (the
+    equal-radius skip over the 210s, the run loop's num00) while landing on
+    the same mv.  step_param 13 leaves NSTEP two steps."""
+    import torch
+    W, H, src, refs = planes
+    jobs = nstep_jobs(M, planes, bw, bh)
+    mvj, mvc = M.default_mv_cost_tables(False)
+    spb, epb = M.sad_per_bit(128), M.error_per_bit(1 << 14)
+    exp, ecl = O.full_pixel_search_batch(src.reshape(-1), refs.reshape(-1), src.shape[1], bw, bh,
+                                         jobs, method, step_param, 0, spb, epb, mvj, mvc,
+                                         skip=skip, cost_list=True, threads=8)
+    if step_param == 0:
+        # the equal-radius skip both fires and does not: a degenerate batch
+        # (every walk alike) would pass without exercising it
+        assert len(np.unique(exp["steps"])) >= 3, np.unique(exp["steps"])
+    cost = M.MvCosts(mvj, mvc).cost_params(spb, epb)
+    out, cl = M.full_pixel_search_batch(torch.from_numpy(src).cuda(), torch.from_numpy(refs).cuda(),
+                                        bw, bh, M.to_device(jobs), cost, method, step_param, skip,
+                                        cost_list=True)
+    got = M.results_numpy(out)
+    for f in ("best_row", "best_col", "bestsme", "steps"):
+        np.testing.assert_array_equal(got[f], exp[f], err_msg=f)
+    np.testing.assert_array_equal(cl.cpu().numpy(), ecl)
