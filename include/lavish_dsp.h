@@ -422,6 +422,190 @@ int lavish_comp_pred_batch(void *comp_pred, const void *pred, int w, int h,
                            int fwd_offset, int bck_offset, int highbd,
                            void *stream);
 
+/* ---- mask building and blending: a64 blends, diff-weighted masks, OBMC ----
+ * What lies between the first-pass convolves and the compound / OBMC
+ * searches above: the blends of av1_make_masked_inter_predictor and
+ * av1_build_obmc_inter_prediction, the DIFFWTD masks, the wsrc / mask streams
+ * lavish_obmc_batch and the OBMC searches read, and the residual reductions
+ * pick_wedge / pick_interinter_seg choose a mask with.  One job = one block;
+ * offsets in ELEMENTS of the array they index; device pointers; asynchronous
+ * on `stream`.  Every call returns 0 for njobs <= 0 and a negative value,
+ * before any device work, for arguments it does not take.
+ * conv_params (a host struct, read before the call returns): round_0 and
+ * round_1 only, as the first pass that filled the d16 buffers had them. */
+typedef struct LavishConvolveParams LavishConvolveParams;
+
+/* dst + job.src_off = blend of src0 + job.ref_off[0] and src1 + job.ref_off[1]
+ * under mask + job.mask_off, each with its own stride; w, h powers of two,
+ * 1..128 (4..128 with d16).
+ *   kind 0: 2-D mask, aom_blend_a64_mask / aom_highbd_blend_a64_mask
+ *           (aom_dsp/blend_a64_mask.c:229-349); subw / subh (0 or 1): the mask
+ *           is twice as wide / high and is averaged down (both: the rounded
+ *           mean of 2x2, one: AOM_BLEND_AVG of the pair); mask_stride >=
+ *           w << subw.  With d16 the inputs are CONV_BUF_TYPE (uint16) blocks
+ *           and dst is u8 (highbd 0) or u16: aom_lowbd_blend_a64_d16_mask /
+ *           aom_highbd_blend_a64_d16_mask (blend_a64_mask.c:36-223).
+ *        1: mask[x], aom_[highbd_]blend_a64_hmask (blend_a64_hmask.c:21-70);
+ *        2: mask[y], aom_[highbd_]blend_a64_vmask (blend_a64_vmask.c:21-70).
+ *   highbd: u16 pixels, bit_depth 8 / 10 / 12; else u8 and bit_depth 8.
+ * dst may be src0 or src1 when the strides are equal (in place); otherwise
+ * the jobs' dst blocks must not overlap any block the call reads. */
+int lavish_blend_a64_batch(void *dst, int dst_stride, const void *src0,
+                           int src0_stride, const void *src1, int src1_stride,
+                           const uint8_t *mask, int mask_stride, int w, int h,
+                           const LavishCompJob *jobs, int njobs, int kind,
+                           int subw, int subh, int d16, int highbd,
+                           int bit_depth,
+                           const LavishConvolveParams *conv_params,
+                           void *stream);
+
+/* mask + job.mask_off (contiguous w x h) from src0 + job.ref_off[0] and src1 +
+ * job.ref_off[1]; job.invert_mask 0: DIFFWTD_38, else DIFFWTD_38_INV.
+ * av1_build_compound_diffwtd_mask (u8), _highbd (highbd 1: u16, the
+ * difference >> (bit_depth - 8) first) and _d16 (d16 1: CONV_BUF_TYPE, the
+ * difference rounded by 2 * FILTER_BITS - round_0 - round_1 + bit_depth - 8)
+ * (av1/common/reconinter.c:296-439).  w, h powers of two, 4..128. */
+int lavish_diffwtd_mask_batch(uint8_t *mask, const void *src0, int src0_stride,
+                              const void *src1, int src1_stride, int w, int h,
+                              const LavishCompJob *jobs, int njobs, int d16,
+                              int highbd, int bit_depth,
+                              const LavishConvolveParams *conv_params,
+                              void *stream);
+
+/* The OBMC pair.  The neighbour walk (foreach_overlappable_nb_above / _left,
+ * av1/common/obmc.h:20-87) needs mode info and stays with the caller; a job
+ * carries its result as two bitmaps: bit k of above_mask (left_mask) is set
+ * when mi column (row) k of the block lies in the span of a neighbour the
+ * walk visited (128 pixels = 32 bits).  above + job.above_off and left +
+ * job.left_off address the neighbours' predictions at the block's own
+ * top-left (pixel (x, y) of the block is at off + y * stride + x); only the
+ * pixels the bitmaps select are read.  obmc_masks: a 127-byte device table,
+ * av1_get_obmc_mask(n) for n = 1, 2, 4 .. 64 back to back (length n starts
+ * at byte n - 1).  (bw, bh): an encoder block size of at least 8x8.  The
+ * record is 48 bytes. */
+typedef struct LavishObmcJob {
+  int64_t src_off;    /* source block; the blend call: the dst block              */
+  int64_t above_off;  /* above prediction at the block's top-left                 */
+  int64_t left_off;   /* left prediction at the block's top-left                  */
+  int64_t wsrc_off;   /* int32 wsrc block, contiguous bw x bh (wsrc call only)    */
+  int64_t mask_off;   /* int32 mask block, contiguous bw x bh (wsrc call only)    */
+  uint32_t above_mask, left_mask;
+} LavishObmcJob;
+
+/* calc_target_weighted_pred (av1/encoder/rdopt.c:6362-6580): the wsrc and
+ * mask blocks lavish_obmc_batch and the OBMC searches read. */
+int lavish_obmc_wsrc_batch(const void *src, int src_stride, const void *above,
+                           int above_stride, const void *left, int left_stride,
+                           int bw, int bh, const LavishObmcJob *jobs, int njobs,
+                           const uint8_t *obmc_masks, int highbd, int32_t *wsrc,
+                           int32_t *mask, void *stream);
+
+/* av1_build_obmc_inter_prediction (av1/common/reconinter.c:844-945) on one
+ * plane, in place on dst + job.src_off: (bw, bh) is the luma block size and
+ * the plane's block is (bw >> subsampling_x) x (bh >> subsampling_y), with
+ * the halved spans and overlaps and av1_skip_u4x4_pred_in_obmc
+ * (reconinter.c:812-830).  Offsets and strides are the plane's. */
+int lavish_obmc_blend_batch(void *dst, int dst_stride, const void *above,
+                            int above_stride, const void *left, int left_stride,
+                            int bw, int bh, int subsampling_x, int subsampling_y,
+                            const LavishObmcJob *jobs, int njobs,
+                            const uint8_t *obmc_masks, int highbd, void *stream);
+
+/* The residual reductions of pick_wedge / pick_interinter_seg
+ * (av1/encoder/wedge_utils.c:52-125) over job.n contiguous elements, n a
+ * multiple of 64 in 64 .. 16384.  The record is 48 bytes.
+ *   kind 0: av1_wedge_compute_delta_squares: (int16_t *)out + job.out_off =
+ *           clamp(a^2 - b^2, INT16_MIN, INT16_MAX);
+ *        1: av1_wedge_sse_from_residuals: a = r1, b = d;
+ *           ((uint64_t *)out)[job] = ROUND_POWER_OF_TWO(sum of
+ *           clamp(64 * r1 + m * d, INT16_MIN, INT16_MAX)^2, 12);
+ *        2: av1_wedge_sign_from_residuals: a = ds (b unused);
+ *           ((int8_t *)out)[job] = sum of ds * m > job.limit. */
+typedef struct LavishWedgeJob {
+  int64_t a_off;    /* r1 / ds / a                                                */
+  int64_t b_off;    /* d / b                                                      */
+  int64_t m_off;    /* u8 mask (kinds 1, 2)                                       */
+  int64_t out_off;  /* kind 0: the d block                                        */
+  int64_t limit;    /* kind 2                                                     */
+  int32_t n;
+  int32_t reserved;
+} LavishWedgeJob;
+int lavish_wedge_batch(const int16_t *a, const int16_t *b, const uint8_t *m,
+                       const LavishWedgeJob *jobs, int njobs, int kind,
+                       void *out, void *stream);
+
+/* Per-call shims (host buffers) with the reference's prototypes; highbd pixel
+ * pointers arrive tagged (CONVERT_TO_BYTEPTR).
+ * aom_dsp/aom_dsp_rtcd_defs.pl:701 */
+void aom_lowbd_blend_a64_d16_mask_hip(uint8_t *dst, uint32_t dst_stride,
+                                      const uint16_t *src0, uint32_t src0_stride,
+                                      const uint16_t *src1, uint32_t src1_stride,
+                                      const uint8_t *mask, uint32_t mask_stride,
+                                      int w, int h, int subw, int subh,
+                                      LavishConvolveParams *conv_params);
+/* aom_dsp_rtcd_defs.pl:703 */
+void aom_blend_a64_mask_hip(uint8_t *dst, uint32_t dst_stride, const uint8_t *src0,
+                            uint32_t src0_stride, const uint8_t *src1,
+                            uint32_t src1_stride, const uint8_t *mask,
+                            uint32_t mask_stride, int w, int h, int subw, int subh);
+/* aom_dsp_rtcd_defs.pl:704 */
+void aom_blend_a64_hmask_hip(uint8_t *dst, uint32_t dst_stride, const uint8_t *src0,
+                             uint32_t src0_stride, const uint8_t *src1,
+                             uint32_t src1_stride, const uint8_t *mask, int w, int h);
+/* aom_dsp_rtcd_defs.pl:705 */
+void aom_blend_a64_vmask_hip(uint8_t *dst, uint32_t dst_stride, const uint8_t *src0,
+                             uint32_t src0_stride, const uint8_t *src1,
+                             uint32_t src1_stride, const uint8_t *mask, int w, int h);
+/* aom_dsp_rtcd_defs.pl:711 */
+void aom_highbd_blend_a64_mask_hip(uint8_t *dst, uint32_t dst_stride,
+                                   const uint8_t *src0, uint32_t src0_stride,
+                                   const uint8_t *src1, uint32_t src1_stride,
+                                   const uint8_t *mask, uint32_t mask_stride, int w,
+                                   int h, int subw, int subh, int bd);
+/* aom_dsp_rtcd_defs.pl:712 */
+void aom_highbd_blend_a64_hmask_hip(uint8_t *dst, uint32_t dst_stride,
+                                    const uint8_t *src0, uint32_t src0_stride,
+                                    const uint8_t *src1, uint32_t src1_stride,
+                                    const uint8_t *mask, int w, int h, int bd);
+/* aom_dsp_rtcd_defs.pl:713 */
+void aom_highbd_blend_a64_vmask_hip(uint8_t *dst, uint32_t dst_stride,
+                                    const uint8_t *src0, uint32_t src0_stride,
+                                    const uint8_t *src1, uint32_t src1_stride,
+                                    const uint8_t *mask, int w, int h, int bd);
+/* aom_dsp_rtcd_defs.pl:714 */
+void aom_highbd_blend_a64_d16_mask_hip(uint8_t *dst, uint32_t dst_stride,
+                                       const uint16_t *src0, uint32_t src0_stride,
+                                       const uint16_t *src1, uint32_t src1_stride,
+                                       const uint8_t *mask, uint32_t mask_stride,
+                                       int w, int h, int subw, int subh,
+                                       LavishConvolveParams *conv_params,
+                                       const int bd);
+/* av1/common/av1_rtcd_defs.pl:257 (mask_type: DIFFWTD_MASK_TYPE, a uint8_t) */
+void av1_build_compound_diffwtd_mask_hip(uint8_t *mask, uint8_t mask_type,
+                                         const uint8_t *src0, int src0_stride,
+                                         const uint8_t *src1, int src1_stride, int h,
+                                         int w);
+/* av1_rtcd_defs.pl:261 */
+void av1_build_compound_diffwtd_mask_highbd_hip(uint8_t *mask, uint8_t mask_type,
+                                                const uint8_t *src0, int src0_stride,
+                                                const uint8_t *src1, int src1_stride,
+                                                int h, int w, int bd);
+/* av1_rtcd_defs.pl:265 */
+void av1_build_compound_diffwtd_mask_d16_hip(uint8_t *mask, uint8_t mask_type,
+                                             const uint16_t *src0, int src0_stride,
+                                             const uint16_t *src1, int src1_stride,
+                                             int h, int w,
+                                             LavishConvolveParams *conv_params, int bd);
+/* av1_rtcd_defs.pl:440 */
+uint64_t av1_wedge_sse_from_residuals_hip(const int16_t *r1, const int16_t *d,
+                                          const uint8_t *m, int N);
+/* av1_rtcd_defs.pl:442 */
+int8_t av1_wedge_sign_from_residuals_hip(const int16_t *ds, const uint8_t *m, int N,
+                                         int64_t limit);
+/* av1_rtcd_defs.pl:444 */
+void av1_wedge_compute_delta_squares_hip(int16_t *d, const int16_t *a,
+                                         const int16_t *b, int N);
+
 /* ---- lossless 4x4 Walsh-Hadamard ----------------------------------------
  * av1_fwht4x4 (hybrid_fwd_txfm.c:24-76): src_diff + job.src_off (stride) ->
  * 16 words at coeff + job.aux_off. */
