@@ -100,6 +100,21 @@ int inter_pred_batch(const void* ref, int ref_stride, int ref_width, int ref_hei
                      const LavishSubpelResult* mvs, void* dst, int dst_stride, int bd, int highbd,
                      const int16_t* custom, int r0, int r1, hipStream_t s);
 
+// lavish_intra_pred_batch with the pixel type apart from the bit depth (the
+// highbd shims take uint16_t pixels at 8 bits too)
+int intra_pred_batch(const void* ref, int ref_stride, void* dst, int dst_stride,
+                     const LavishIntraJob* jobs, int njobs, int bd, int highbd, hipStream_t s);
+// single-call kernels behind the intra shims (intra.hip), device pointers:
+// one z1 / z2 / z3 block (zone 1 .. 3) from finished edges, above[i] =
+// above_dev[i - a_lo] for a_n elements (left alike), into a compact w x h dst;
+// and av1_filter_intra_edge / av1_upsample_intra_edge in place on p = buf + 2
+// of an n-element buffer
+int intra_dr_single(void* dst, const void* above, int a_lo, int a_n, const void* left, int l_lo,
+                    int l_n, int zone, int w, int h, int ua, int ul, int dx, int dy, int highbd,
+                    hipStream_t s);
+int intra_edge_single(void* buf, int n, int sz, int strength, int upsample, int bd, int highbd,
+                      hipStream_t s);
+
 // fork / join over the library's per-thread internal streams
 int fan_width();
 int set_fan_width(int w);

@@ -16,7 +16,8 @@ The full-pel step runs with the reference's per-block start-mv selection
 (tpl_motion_search: neighbouring tpl mvs, is_alike_mv, prune_starting_mv;
 a device wavefront, since each block needs its finished neighbours) or,
 with neighbour_starts=False, from the jobs' start mvs.  Intra candidates
-stay with the caller."""
+are not part of TplFrame: lavish_dsp.intra predicts them (any list of modes
+into a [nmodes, H, W] tensor) and tpl_block_batch costs that tensor."""
 import ctypes
 
 import numpy as np

@@ -1942,6 +1942,100 @@ void av1_highbd_convolve_2d_scale_hip(const uint16_t *src, int src_stride, uint1
                                       const int subpel_y_qn, const int y_step_qn,
                                       LavishConvolveParams *conv_params, int bd);
 
+/* ---- intra prediction ------------------------------------------------------
+ * lavish_intra_pred_batch is build_intra_predictors / build_intra_predictors_high
+ * (av1/common/reconintra.c:1133-1477) for a list of jobs, bit-exact: edge
+ * assembly from the counts, the non-directional predictors, the directional
+ * path (corner filter, edge filter, upsampling, z1 / z2 / z3) and filter
+ * intra.  A job carries what av1_predict_intra_block hands down
+ * (reconintra.c:1634-1650); the availability walk (has_top_right /
+ * has_bottom_left, get_intra_edge_filter_type) stays with the caller.
+ * Planes and jobs are device memory; pixels are uint8_t for bit_depth 8 and
+ * uint16_t for 10 / 12.  Jobs of any sizes and modes mix in one call.  A job
+ * reads only the pixels its counts declare available, and reads all of them
+ * before its first store, so dst may be the plane ref points into; jobs of one
+ * call must not read what another job of the call writes.  Asynchronous on
+ * `stream`.  Returns 0, or a negative value for a refused argument (null
+ * plane, bit_depth not 8 / 10 / 12); njobs <= 0 is a no-op.  A job whose
+ * tx_size / mode / filter_intra_mode is out of range (or filter intra above
+ * 32x32, or a directional mode whose p_angle is not its base angle + 3 * delta,
+ * delta in -3 .. 3) is skipped on the device: validate on the host
+ * (lavish_dsp.intra.intra_jobs does).  The record is 48 bytes. */
+typedef struct LavishIntraJob {
+  int64_t ref_off;  /* element offset of the block's top-left pixel in ref        */
+  int64_t dst_off;  /* and in dst                                                 */
+  uint8_t tx_size;  /* TX_4X4 .. TX_64X16 (0 .. 18)                               */
+  uint8_t mode;     /* DC_PRED .. PAETH_PRED (0 .. 12)                            */
+  uint8_t filter_intra_mode;      /* 0 .. 4; 5 (FILTER_INTRA_MODES): none         */
+  uint8_t disable_edge_filter;
+  uint8_t intra_edge_filter_type; /* 0 or 1                                       */
+  uint8_t reserved[3];
+  int32_t p_angle;                /* directional modes: base angle + 3 * delta    */
+  int32_t n_top_px, n_topright_px;    /* -1 for a corner count: not needed        */
+  int32_t n_left_px, n_bottomleft_px;
+  int32_t reserved2;
+} LavishIntraJob;
+int lavish_intra_pred_batch(const void *ref, int ref_stride, void *dst, int dst_stride,
+                            const LavishIntraJob *jobs, int njobs, int bit_depth,
+                            void *stream);
+/* the tables of csrc/intra_tables.h (for tests): which = 0 smooth weights
+ * [124], 1 derivative by angle [90], 2 filter-intra taps [5][8][8], 3 edge
+ * kernels [3][5], 4 mode to angle [13]; copies up to `cap` values into out as
+ * int32 and returns the table's length (0: no such table) */
+int lavish_intra_table(int which, int32_t *out, int cap);
+
+/* Per-call shims (host buffers) with the reference's prototypes.
+ * aom_dsp/aom_dsp_rtcd_defs.pl:60-86: the ten predictor families over the 19
+ * block sizes, 8-bit and highbd (uint16_t pointers, not tagged): 380 entries.
+ * above / left are read at the reference's extents (above[-1] for paeth). */
+#define LAVISH_INTRA_SIZES(X, t)                                                     \
+  X(t, 4, 4) X(t, 8, 8) X(t, 16, 16) X(t, 32, 32) X(t, 64, 64) X(t, 4, 8) X(t, 8, 4) \
+  X(t, 8, 16) X(t, 16, 8) X(t, 16, 32) X(t, 32, 16) X(t, 32, 64) X(t, 64, 32)        \
+  X(t, 4, 16) X(t, 16, 4) X(t, 8, 32) X(t, 32, 8) X(t, 16, 64) X(t, 64, 16)
+#define LAVISH_INTRA_TYPES(X)                                                          \
+  LAVISH_INTRA_SIZES(X, dc) LAVISH_INTRA_SIZES(X, dc_top) LAVISH_INTRA_SIZES(X, dc_left) \
+  LAVISH_INTRA_SIZES(X, dc_128) LAVISH_INTRA_SIZES(X, v) LAVISH_INTRA_SIZES(X, h)      \
+  LAVISH_INTRA_SIZES(X, paeth) LAVISH_INTRA_SIZES(X, smooth)                           \
+  LAVISH_INTRA_SIZES(X, smooth_v) LAVISH_INTRA_SIZES(X, smooth_h)
+#define LAVISH_INTRA_DECL(t, W, H)                                                   \
+  void aom_##t##_predictor_##W##x##H##_hip(uint8_t *dst, ptrdiff_t y_stride,         \
+                                           const uint8_t *above, const uint8_t *left); \
+  void aom_highbd_##t##_predictor_##W##x##H##_hip(uint16_t *dst, ptrdiff_t y_stride, \
+                                                  const uint16_t *above,             \
+                                                  const uint16_t *left, int bd);
+LAVISH_INTRA_TYPES(LAVISH_INTRA_DECL)
+#undef LAVISH_INTRA_DECL
+/* av1/common/av1_rtcd_defs.pl:105-114 */
+void av1_dr_prediction_z1_hip(uint8_t *dst, ptrdiff_t stride, int bw, int bh,
+                              const uint8_t *above, const uint8_t *left,
+                              int upsample_above, int dx, int dy);
+void av1_dr_prediction_z2_hip(uint8_t *dst, ptrdiff_t stride, int bw, int bh,
+                              const uint8_t *above, const uint8_t *left,
+                              int upsample_above, int upsample_left, int dx, int dy);
+void av1_dr_prediction_z3_hip(uint8_t *dst, ptrdiff_t stride, int bw, int bh,
+                              const uint8_t *above, const uint8_t *left,
+                              int upsample_left, int dx, int dy);
+/* tx_size: TX_SIZE; up to 32x32 */
+void av1_filter_intra_predictor_hip(uint8_t *dst, ptrdiff_t stride, uint8_t tx_size,
+                                    const uint8_t *above, const uint8_t *left, int mode);
+/* av1_rtcd_defs.pl:247-253 */
+void av1_highbd_dr_prediction_z1_hip(uint16_t *dst, ptrdiff_t stride, int bw, int bh,
+                                     const uint16_t *above, const uint16_t *left,
+                                     int upsample_above, int dx, int dy, int bd);
+void av1_highbd_dr_prediction_z2_hip(uint16_t *dst, ptrdiff_t stride, int bw, int bh,
+                                     const uint16_t *above, const uint16_t *left,
+                                     int upsample_above, int upsample_left, int dx, int dy,
+                                     int bd);
+void av1_highbd_dr_prediction_z3_hip(uint16_t *dst, ptrdiff_t stride, int bw, int bh,
+                                     const uint16_t *above, const uint16_t *left,
+                                     int upsample_left, int dx, int dy, int bd);
+/* av1_rtcd_defs.pl:605-613: in place on p (the upsampler
+ * writes p[-2 .. 2 * sz - 2], both ends included: 2 * sz + 1 elements) */
+void av1_filter_intra_edge_hip(uint8_t *p, int sz, int strength);
+void av1_upsample_intra_edge_hip(uint8_t *p, int sz);
+void av1_filter_intra_edge_high_hip(uint16_t *p, int sz, int strength);
+void av1_upsample_intra_edge_high_hip(uint16_t *p, int sz, int bd);
+
 #ifdef __cplusplus
 }
 #endif
