@@ -739,3 +739,75 @@ def pick_lower_besterr(a, b):
     # besterr is uint32 at most INT_MAX + a small mv cost: compare as unsigned
     ea, eb = ra[:, 1].to(torch.int64) & 0xFFFFFFFF, rb[:, 1].to(torch.int64) & 0xFFFFFFFF
     return torch.where((eb < ea)[:, None], rb, ra).contiguous().view(torch.uint8).view(-1)
+
+
+# ------------------------------------- high bit depth (uint16 planes) ------
+_lib.lavish_highbd_full_pixel_search_batch.argtypes = [
+    _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, ctypes.POINTER(MvCostParams),
+    _i32, _vp, _vp, _vp]
+_lib.lavish_highbd_full_pixel_search_batch.restype = _i32
+_lib.lavish_highbd_find_best_sub_pixel_tree_batch.argtypes = [
+    _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32,
+    ctypes.POINTER(MvCostParams), _vp, _vp, _vp]
+_lib.lavish_highbd_find_best_sub_pixel_tree_batch.restype = _i32
+
+
+def _hbd_planes(src, ref):
+    import torch
+    ok = (torch.int16, torch.uint16)
+    assert src.dtype in ok and ref.dtype in ok, "planes must be int16 / uint16 tensors"
+    assert src.is_contiguous() and ref.is_contiguous(), "planes must be C-contiguous"
+
+
+def highbd_full_pixel_search_batch(src, ref, w, h, jobs, cost, bit_depth=10, method="diamond",
+                                   step_param=0, use_downsampled_sad=False, cost_list=False,
+                                   out=None, cost_lists=None, stream=None):
+    """lavish_highbd_full_pixel_search_batch: full_pixel_search_batch over
+    int16 / uint16 device planes holding `bit_depth`-bit pixels (8, 10 or 12)
+    for the methods "diamond", "nstep" and "nstep_8pt"; the jobs' offsets and
+    the stride are in elements.  Returns (RESULT_DTYPE byte tensor, int32
+    [n, 5] cost lists or None)."""
+    import torch
+    _hbd_planes(src, ref)
+    nj = jobs.numel() // JOB_DTYPE.itemsize
+    if out is None:
+        out = torch.empty(nj * RESULT_DTYPE.itemsize, dtype=torch.uint8, device=src.device)
+    if cost_list and cost_lists is None:
+        cost_lists = torch.empty((nj, 5), dtype=torch.int32, device=src.device)
+    rc = _lib.lavish_highbd_full_pixel_search_batch(
+        _vp(src.data_ptr()), src.stride(0), _vp(ref.data_ptr()), src.stride(0), w, h, bit_depth,
+        _vp(jobs.data_ptr()), nj, SEARCH_METHODS[method], step_param, ctypes.byref(cost),
+        int(use_downsampled_sad), _vp(out.data_ptr()),
+        _vp(cost_lists.data_ptr()) if cost_list else None, _stream_ptr(stream))
+    if rc != 0:
+        raise ValueError("lavish_highbd_full_pixel_search_batch rejected its arguments (rc=%d)"
+                         % rc)
+    return out, (cost_lists if cost_list else None)
+
+
+def highbd_find_best_sub_pixel_tree_batch(src, ref, w, h, jobs, cost, bit_depth=10,
+                                          method="pruned_more", forced_stop=EIGHTH_PEL,
+                                          allow_hp=False, iters_per_step=1, fullpel=None,
+                                          cost_lists=None, out=None, stream=None):
+    """lavish_highbd_find_best_sub_pixel_tree_batch:
+    find_best_sub_pixel_tree_batch (the bilinear error) over int16 / uint16
+    device planes holding `bit_depth`-bit pixels; fullpel / cost_lists: what
+    highbd_full_pixel_search_batch returned, still on the device."""
+    import torch
+    _hbd_planes(src, ref)
+    nj = jobs.numel() // SUBPEL_JOB_DTYPE.itemsize
+    if fullpel is not None:
+        assert fullpel.numel() >= nj * RESULT_DTYPE.itemsize
+    if cost_lists is not None:
+        assert cost_lists.dtype == torch.int32 and cost_lists.numel() >= 5 * nj
+    out = _subpel_out(nj, out, src.device)
+    rc = _lib.lavish_highbd_find_best_sub_pixel_tree_batch(
+        _vp(src.data_ptr()), src.stride(0), _vp(ref.data_ptr()), src.stride(0), w, h, bit_depth,
+        _vp(jobs.data_ptr()), None if fullpel is None else _vp(fullpel.data_ptr()), nj,
+        SUBPEL_METHODS[method], forced_stop, int(allow_hp), iters_per_step, ctypes.byref(cost),
+        None if cost_lists is None else _vp(cost_lists.data_ptr()), _vp(out.data_ptr()),
+        _stream_ptr(stream))
+    if rc != 0:
+        raise ValueError("lavish_highbd_find_best_sub_pixel_tree_batch rejected its arguments "
+                         "(rc=%d)" % rc)
+    return out

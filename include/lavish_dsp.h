@@ -1120,6 +1120,58 @@ int lavish_find_best_sub_pixel_tree_batch_ex(
     int allow_hp, int iters_per_step, const LavishMvCostParams *cost,
     const int32_t *cost_lists, LavishSubpelResult *out, void *stream);
 
+/* ---- high bit depth (8 / 10 / 12 bits on uint16_t planes) ----------------
+ * The single-reference searches with the members highbd_set_var_fns binds
+ * (av1/encoder/encoder_utils.h:130-230,572-), csrc/mcomp_hbd.hip and
+ * csrc/subpel_hbd.hip, one wave per job.  Jobs and results are the 8-bit
+ * entry points' records; src_stride, ref_stride and the jobs' src_off /
+ * ref_off are in ELEMENTS (uint16_t), not bytes.  bit_depth: 8, 10 or 12
+ * (pixel values below 1 << bit_depth).
+ *
+ * lavish_highbd_full_pixel_search_batch: av1_full_pixel_search
+ * (av1/encoder/mcomp.c:1755-1873, no mesh) for search_method DIAMOND 0,
+ * NSTEP 1 or NSTEP_8PT 2 (the pattern methods: -4), sdf / sdx4df / sdsf =
+ * aom_highbd_sad{W}x{H}[x4d] / aom_highbd_sad_skip_{W}x{H} under the
+ * _bits8 / _bits10 / _bits12 wrappers (the block's SAD >> 0 / 2 / 4, before
+ * the mv SAD cost is added), vf = aom_highbd_{8,10,12}_variance{W}x{H}, any
+ * mv cost, use_downsampled_sad with the recheck on the wrapped SADs, and
+ * the cost list (calc_int_sad_list) when cost_lists is not NULL.
+ * Padding: both planes must be padded so that every mv inside the limits
+ * addresses memory; the kernel reads rows of exactly w elements at the
+ * pixel's own address: no slack before a row's start or after its end.
+ * Returns 0 (also for njobs <= 0), -7 NULL src / ref / jobs / out or a
+ * bit_depth outside {8, 10, 12}, -4 unsupported method, -1 bad step_param,
+ * -2 bad cost parameters, -3 unsupported w x h; every refusal comes before
+ * any device work and leaves out untouched. */
+int lavish_highbd_full_pixel_search_batch(
+    const uint16_t *src, int src_stride, const uint16_t *ref, int ref_stride,
+    int w, int h, int bit_depth, const LavishDiamondJob *jobs, int njobs,
+    int search_method, int step_param, const LavishMvCostParams *cost,
+    int use_downsampled_sad, LavishDiamondResult *out, int32_t *cost_lists,
+    void *stream);
+
+/* lavish_highbd_find_best_sub_pixel_tree_batch: the sub-pel methods of
+ * lavish_find_best_sub_pixel_tree_batch (SUBPEL_TREE with USE_2_TAPS_ORIG,
+ * SUBPEL_TREE_PRUNED, SUBPEL_TREE_PRUNED_MORE) with svf =
+ * aom_highbd_{8,10,12}_sub_pixel_variance{W}x{H} (aom_dsp/variance.c:
+ * 454-670) and setup_center_error through the high-bit-depth vf; fullpel and
+ * cost_lists (device) are what lavish_highbd_full_pixel_search_batch wrote,
+ * so the pair chains on the device as the 8-bit pair does.
+ * Padding: for every mv inside the SubpelMvLimits the (w + 1) x (h + 1)
+ * elements at the mv's full-pel floor must address memory (the bilinear
+ * filter's own reach); the kernel reads exactly those: no further slack.
+ * Returns 0 (also for njobs <= 0), -7 NULL src / ref / jobs / out or a
+ * bit_depth outside {8, 10, 12}, then as the 8-bit call: -1 bad forced_stop,
+ * -2 bad cost parameters, -4 bad iters_per_step, -6 unsupported method,
+ * -3 unsupported w x h; all before any device work. */
+int lavish_highbd_find_best_sub_pixel_tree_batch(
+    const uint16_t *src, int src_stride, const uint16_t *ref, int ref_stride,
+    int w, int h, int bit_depth, const LavishSubpelJob *jobs,
+    const LavishDiamondResult *fullpel, int njobs, int subpel_search_method,
+    int forced_stop, int allow_hp, int iters_per_step,
+    const LavishMvCostParams *cost, const int32_t *cost_lists,
+    LavishSubpelResult *out, void *stream);
+
 /* The compound, masked and OBMC sub-pel searches (csrc/subpel_comp.hip),
  * 8-bit, unscaled reference, one wave per job: what follows
  * lavish_comp_full_pixel_search_batch / lavish_refining_search_8p_batch in
