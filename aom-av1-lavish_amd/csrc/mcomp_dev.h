@@ -1,6 +1,6 @@
 // mcomp_dev.h -- the device layer of the full-pixel motion searches for gfx950
-// (C3), shared by mcomp.hip, mcomp_tpl.hip and mcomp_lj.hip and included by
-// nothing else.
+// (C3), shared by mcomp.hip, mcomp_tpl.hip, mcomp_lj.hip, mcomp_comp.hip,
+// mcomp_hbd.hip and mcomp_comp_hbd.hip and included by nothing else.
 //
 // Reference (one block, one reference frame, one CPU thread):
 //   av1_full_pixel_search (av1/encoder/mcomp.c:1755-1895, method DIAMOND)
@@ -325,6 +325,38 @@ __device__ void sad_and_skip(const Ctx& c, int lane, int row, int col, int& sad,
   const uint32_t ta = groups_sum(group_sum8(all)), te = groups_sum(group_sum8(even));
   sad = (int)ta;
   ssad = (int)(2 * te);
+}
+
+// ---- high bit depth (mcomp_hbd.hip, mcomp_comp_hbd.hip) ----
+// v_sad_u16 over a dword of two pixels
+__device__ __forceinline__ uint32_t sad2(uint32_t a, uint32_t b, uint32_t acc) {
+  return __builtin_amdgcn_sad_u16(a, b, acc);
+}
+
+// the wave total of per-lane u32 values as 64 bits (two 32-bit reductions of
+// the low 24 and the high 8 bits)
+__device__ __forceinline__ uint64_t groups_sum64(uint32_t v) {
+  const uint32_t lo = groups_sum(group_sum8(v & 0xFFFFFFu));
+  const uint32_t hi = groups_sum(group_sum8(v >> 24));
+  return ((uint64_t)hi << 24) + lo;
+}
+
+// aom_highbd_{8,10,12}_variance from the exact sums (variance.c:351-408):
+// 8 bits truncate, 10 / 12 round sse by 2 * sh and the signed sum by sh (an
+// arithmetic shift) and clamp the variance at 0
+__device__ __forceinline__ uint32_t hbd_var_tail(int64_t sum64, uint64_t sse64, int sh, int n,
+                                                 uint32_t* sse_out = nullptr) {
+  if (sh == 0) {
+    const uint32_t sse = (uint32_t)sse64;
+    const int sum = (int)sum64;
+    if (sse_out) *sse_out = sse;
+    return sse - (uint32_t)(((int64_t)sum * sum) / n);
+  }
+  const uint32_t sse = (uint32_t)((sse64 + ((1ull << (2 * sh)) >> 1)) >> (2 * sh));
+  const int sum = (int)((sum64 + ((1 << sh) >> 1)) >> sh);
+  if (sse_out) *sse_out = sse;
+  const int64_t var = (int64_t)sse - ((int64_t)sum * sum) / n;
+  return var >= 0 ? (uint32_t)var : 0u;
 }
 
 // sdf (full-row SAD) of a 16x16 block at up to 4 full-pel positions (r[k],

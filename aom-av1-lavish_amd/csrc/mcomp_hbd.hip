@@ -29,10 +29,6 @@
 namespace lavish {
 namespace {
 
-__device__ __forceinline__ uint32_t sad2(uint32_t a, uint32_t b, uint32_t acc) {
-  return __builtin_amdgcn_sad_u16(a, b, acc);
-}
-
 template <int W, int H, bool SKIP>
 struct HbdSearch {
   using G = Geo<2 * W, H, SKIP>;  // in bytes: DW = W / 2 dwords per row
@@ -92,32 +88,6 @@ struct HbdSearch {
     return (SKIP ? 2 * acc : acc) >> sh;
   }
 };
-
-// the wave total of per-lane u32 values as 64 bits (two 32-bit reductions of
-// the low 24 and the high 8 bits)
-__device__ __forceinline__ uint64_t groups_sum64(uint32_t v) {
-  const uint32_t lo = groups_sum(group_sum8(v & 0xFFFFFFu));
-  const uint32_t hi = groups_sum(group_sum8(v >> 24));
-  return ((uint64_t)hi << 24) + lo;
-}
-
-// aom_highbd_{8,10,12}_variance from the exact sums (variance.c:351-408):
-// 8 bits truncate, 10 / 12 round sse by 2 * sh and the signed sum by sh (an
-// arithmetic shift) and clamp the variance at 0
-__device__ __forceinline__ uint32_t hbd_var_tail(int64_t sum64, uint64_t sse64, int sh, int n,
-                                                 uint32_t* sse_out = nullptr) {
-  if (sh == 0) {
-    const uint32_t sse = (uint32_t)sse64;
-    const int sum = (int)sum64;
-    if (sse_out) *sse_out = sse;
-    return sse - (uint32_t)(((int64_t)sum * sum) / n);
-  }
-  const uint32_t sse = (uint32_t)((sse64 + ((1ull << (2 * sh)) >> 1)) >> (2 * sh));
-  const int sum = (int)((sum64 + ((1 << sh) >> 1)) >> sh);
-  if (sse_out) *sse_out = sse;
-  const int64_t var = (int64_t)sse - ((int64_t)sum * sum) / n;
-  return var >= 0 ? (uint32_t)var : 0u;
-}
 
 // one 4-pixel unit (two dwords) of source a and reference b
 __device__ __forceinline__ void hbd_acc4(const uint32_t (&a)[2], const uint32_t (&b)[2], int& sum,

@@ -59,7 +59,6 @@ static_assert(sizeof(LavishSubpelResult) == 16 && sizeof(LavishCompSearchResult)
               "result layout");
 
 constexpr int kInvalidMv = -32768;  // MARK_MV_INVALID
-constexpr int kMvMax = (1 << 14) - 1;
 
 // the 4 bytes at p, any byte address, nothing past them
 __device__ __forceinline__ uint32_t load4(const uint8_t* p) {
@@ -102,19 +101,6 @@ struct Regs {
 // the blend weights of the candidate: the mask bytes, or 64 - them
 __device__ __forceinline__ uint32_t fold_mask(uint32_t m, int invert) {
   return invert ? 0x40404040u - m : m;  // (every byte <= 64: no borrow)
-}
-
-// estimate_obmc_mvcost (mcomp.c:3561-3583): the diff through GET_MV_SUBPEL
-// (x 8), int arithmetic, 13-bit rounding; MV_COST_NONE 0 (the L1 types are
-// refused by the entry point).  The reference indexes its tables without a
-// bound; here the index stays inside them.
-__device__ __forceinline__ int obmc_estimate_cost(const Ctx& c, int row, int col) {
-  if (!c.entropy) return 0;
-  const int dr = min(max(8 * (row - c.ref_mv_row), -kMvMax), kMvMax);
-  const int dc = min(max(8 * (col - c.ref_mv_col), -kMvMax), kMvMax);
-  const int joint = (dc != 0) | ((dr != 0) << 1);
-  const uint32_t rate = (uint32_t)(c.mvjcost[joint] + c.mvcost0[dr] + c.mvcost1[dc]);
-  return (int)((uint32_t)((int)(rate * (uint32_t)c.error_per_bit + 4096u) >> 13));
 }
 
 // segment sg of the prediction v against the job's invariants -- the source,

@@ -1,6 +1,8 @@
 // subpel_dev.h -- what the sub-pel search kernels share (subpel.hip: the
 // single-reference searches; subpel_comp.hip: the compound, masked and OBMC
-// ones): the wave shape (Sp), the byte-window loads, the horizontal 8-tap
+// ones; subpel_hbd.hip and subpel_comp_hbd.hip: the same two at high bit
+// depth, with the u16 window loads and the depth's variance they share):
+// the wave shape (Sp), the byte-window loads, the horizontal 8-tap
 // pass, the wave reduction, the kernel tables and the best-mv record; and
 // the search itself -- the mv part of a context (MvCtx, mv_cost, in_range),
 // the strictly-better update (settle), the centre error, the candidate
@@ -139,6 +141,54 @@ __device__ __forceinline__ int mv_cost(const MvCtx& c, int row, int col) {
 }
 __device__ __forceinline__ bool in_range(const MvLimits& c, int row, int col) {
   return col >= c.col_min && col <= c.col_max && row >= c.row_min && row <= c.row_max;
+}
+
+constexpr int kMvMax = (1 << 14) - 1;
+
+// estimate_obmc_mvcost (mcomp.c:3561-3583): the diff through GET_MV_SUBPEL
+// (x 8), int arithmetic, 13-bit rounding; MV_COST_NONE 0 (the L1 types are
+// refused by the entry point).  The reference indexes its tables without a
+// bound; here the index stays inside them.
+__device__ __forceinline__ int obmc_estimate_cost(const MvCtx& c, int row, int col) {
+  if (!c.entropy) return 0;
+  const int dr = min(max(8 * (row - c.ref_mv_row), -kMvMax), kMvMax);
+  const int dc = min(max(8 * (col - c.ref_mv_col), -kMvMax), kMvMax);
+  const int joint = (dc != 0) | ((dr != 0) << 1);
+  const uint32_t rate = (uint32_t)(c.mvjcost[joint] + c.mvcost0[dr] + c.mvcost1[dc]);
+  return (int)((uint32_t)((int)(rate * (uint32_t)c.error_per_bit + 4096u) >> 13));
+}
+
+// ------------------------------------------- high bit depth (uint16_t planes) --
+// 8 bytes (4 pixels) at p, any byte address
+__device__ __forceinline__ void load8(const uint8_t* p, uint32_t (&o)[2]) {
+  typedef const __attribute__((address_space(1))) u32x2u* g2;
+  const u32x2u v = *(g2)(uintptr_t)p;
+  o[0] = v.x;
+  o[1] = v.y;
+}
+// pixels 0..4 at p: (dwords of pixels 0-1 and 2-3, pixel 4)
+__device__ __forceinline__ void load5p(const uint8_t* p, uint32_t (&o)[2], uint32_t& p4) {
+  typedef const __attribute__((address_space(1))) u32u* g1;
+  load8(p, o);
+  p4 = *(g1)(uintptr_t)(p + 6) >> 16;
+}
+
+// aom_highbd_{8,10,12}_variance of the wave's totals (variance.c:351-408) for a
+// context with the depth's shift sh = bit_depth - 8
+template <int W, int H, class C>
+__device__ __forceinline__ uint32_t hbd_variance(const C& c, int sum, uint32_t sse,
+                                                 uint32_t& sse_out) {
+  const int ts = (int)wave_total((uint32_t)sum);  // |.| <= 2^14 * 4095
+  const uint64_t tq = ((uint64_t)wave_total(sse >> 24) << 24) + wave_total(sse & 0xFFFFFFu);
+  if (c.sh == 0) {
+    sse_out = (uint32_t)tq;
+    return sse_out - (uint32_t)(((int64_t)ts * ts) / (W * H));
+  }
+  sse_out = (uint32_t)((tq + ((1ull << (2 * c.sh)) >> 1)) >> (2 * c.sh));
+  // ROUND_POWER_OF_TWO of the signed sum: an arithmetic shift
+  const int rs = (ts + ((1 << c.sh) >> 1)) >> c.sh;
+  const int64_t var = (int64_t)sse_out - ((int64_t)rs * rs) / (W * H);
+  return var >= 0 ? (uint32_t)var : 0u;
 }
 
 // ------------------------------------------------------------------ the tree --

@@ -54,19 +54,6 @@ struct HRegs {
   uint32_t sv[HSp<W, H>::NS][2];
 };
 
-__device__ __forceinline__ void load8(const uint8_t* p, uint32_t (&o)[2]) {
-  typedef const __attribute__((address_space(1))) u32x2u* g2;
-  const u32x2u v = *(g2)(uintptr_t)p;
-  o[0] = v.x;
-  o[1] = v.y;
-}
-// pixels 0..4 at p: (dwords of pixels 0-1 and 2-3, pixel 4)
-__device__ __forceinline__ void load5p(const uint8_t* p, uint32_t (&o)[2], uint32_t& p4) {
-  typedef const __attribute__((address_space(1))) u32u* g1;
-  load8(p, o);
-  p4 = *(g1)(uintptr_t)(p + 6) >> 16;
-}
-
 // aom_highbd_var_filter_block2d_bil_first / second_pass of the 4 pixels at
 // (y, x) against source words sw: (sum, sse) of prediction - source
 __device__ __forceinline__ void hseg4(const HbdCtx& c, const uint8_t* base, int y, int x,
@@ -122,23 +109,6 @@ __device__ __forceinline__ void seg_err(const HbdCtx& c, const HRegs<W, H>& R, i
 template <int W, int H>
 __device__ __forceinline__ int cand_cost(const HbdCtx& c, const HRegs<W, H>&, int row, int col) {
   return mv_cost(c, row, col);
-}
-
-// aom_highbd_{8,10,12}_variance of the wave's totals (variance.c:351-408)
-template <int W, int H>
-__device__ __forceinline__ uint32_t hbd_variance(const HbdCtx& c, int sum, uint32_t sse,
-                                                 uint32_t& sse_out) {
-  const int ts = (int)wave_total((uint32_t)sum);  // |.| <= 2^14 * 4095
-  const uint64_t tq = ((uint64_t)wave_total(sse >> 24) << 24) + wave_total(sse & 0xFFFFFFu);
-  if (c.sh == 0) {
-    sse_out = (uint32_t)tq;
-    return sse_out - (uint32_t)(((int64_t)ts * ts) / (W * H));
-  }
-  sse_out = (uint32_t)((tq + ((1ull << (2 * c.sh)) >> 1)) >> (2 * c.sh));
-  // ROUND_POWER_OF_TWO of the signed sum: an arithmetic shift
-  const int rs = (ts + ((1 << c.sh) >> 1)) >> c.sh;
-  const int64_t var = (int64_t)sse_out - ((int64_t)rs * rs) / (W * H);
-  return var >= 0 ? (uint32_t)var : 0u;
 }
 
 // subpel_dev.h's settle for this context: the depth's variance

@@ -811,3 +811,146 @@ def highbd_find_best_sub_pixel_tree_batch(src, ref, w, h, jobs, cost, bit_depth=
         raise ValueError("lavish_highbd_find_best_sub_pixel_tree_batch rejected its arguments "
                          "(rc=%d)" % rc)
     return out
+
+
+# ------------------ high bit depth: compound / masked / OBMC searches ------
+_lib.lavish_highbd_comp_full_pixel_search_batch.argtypes = [
+    _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, ctypes.POINTER(MvCostParams),
+    _vp, _vp, _i32, _vp, _vp]
+_lib.lavish_highbd_comp_full_pixel_search_batch.restype = _i32
+_lib.lavish_highbd_refining_search_8p_batch.argtypes = [
+    _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _i32, ctypes.POINTER(MvCostParams), _vp, _vp,
+    _i32, _vp, _vp]
+_lib.lavish_highbd_refining_search_8p_batch.restype = _i32
+_lib.lavish_highbd_obmc_full_pixel_search_batch.argtypes = [
+    _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, ctypes.POINTER(MvCostParams), _i32, _vp,
+    _vp, _vp, _vp]
+_lib.lavish_highbd_obmc_full_pixel_search_batch.restype = _i32
+_lib.lavish_highbd_comp_find_best_sub_pixel_tree_batch.argtypes = [
+    _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
+    ctypes.POINTER(MvCostParams), _vp, _vp, _i32, _vp, _vp]
+_lib.lavish_highbd_comp_find_best_sub_pixel_tree_batch.restype = _i32
+_lib.lavish_highbd_obmc_find_best_sub_pixel_tree_batch.argtypes = [
+    _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.POINTER(MvCostParams),
+    _vp, _vp, _vp, _vp]
+_lib.lavish_highbd_obmc_find_best_sub_pixel_tree_batch.restype = _i32
+
+
+def _ptr16(t):
+    """A contiguous int16 / uint16 device tensor's address, or None."""
+    import torch
+    if t is None:
+        return None
+    assert t.dtype in (torch.int16, torch.uint16) and t.is_contiguous()
+    return _vp(t.data_ptr())
+
+
+def highbd_comp_full_pixel_search_batch(src, ref, w, h, jobs, cost, second_pred, mask=None,
+                                        mask_stride=0, bit_depth=10, method="diamond",
+                                        step_param=0, out=None, stream=None):
+    """lavish_highbd_comp_full_pixel_search_batch: comp_full_pixel_search_batch
+    over int16 / uint16 device planes holding `bit_depth`-bit pixels (8, 10
+    or 12); second_pred an int16 / uint16 tensor, mask uint8 (or None for the
+    average); every offset and the stride in elements."""
+    import torch
+    _hbd_planes(src, ref)
+    nj = jobs.numel() // COMP_JOB_DTYPE.itemsize
+    out = _comp_out(nj, out, src.device)
+    rc = _lib.lavish_highbd_comp_full_pixel_search_batch(
+        _vp(src.data_ptr()), src.stride(0), _vp(ref.data_ptr()), src.stride(0), w, h, bit_depth,
+        _vp(jobs.data_ptr()), nj, SEARCH_METHODS[method], step_param, ctypes.byref(cost),
+        _ptr16(second_pred), _ptr(mask, torch.uint8), mask_stride, _vp(out.data_ptr()),
+        _stream_ptr(stream))
+    if rc != 0:
+        raise ValueError("lavish_highbd_comp_full_pixel_search_batch rejected its arguments "
+                         "(rc=%d)" % rc)
+    return out
+
+
+def highbd_refining_search_8p_batch(src, ref, w, h, jobs, cost, second_pred=None, mask=None,
+                                    mask_stride=0, bit_depth=10, out=None, stream=None):
+    """lavish_highbd_refining_search_8p_batch: refining_search_8p_batch over
+    int16 / uint16 planes; second_pred None: the plain SAD."""
+    import torch
+    _hbd_planes(src, ref)
+    nj = jobs.numel() // COMP_JOB_DTYPE.itemsize
+    out = _comp_out(nj, out, src.device)
+    rc = _lib.lavish_highbd_refining_search_8p_batch(
+        _vp(src.data_ptr()), src.stride(0), _vp(ref.data_ptr()), src.stride(0), w, h, bit_depth,
+        _vp(jobs.data_ptr()), nj, ctypes.byref(cost), _ptr16(second_pred),
+        _ptr(mask, torch.uint8), mask_stride, _vp(out.data_ptr()), _stream_ptr(stream))
+    if rc != 0:
+        raise ValueError("lavish_highbd_refining_search_8p_batch rejected its arguments (rc=%d)"
+                         % rc)
+    return out
+
+
+def highbd_obmc_full_pixel_search_batch(ref, ref_stride, w, h, jobs, cost, wsrc, obmc_mask,
+                                        bit_depth=10, method="diamond", step_param=0,
+                                        fast_obmc_search=False, out=None, stream=None):
+    """lavish_highbd_obmc_full_pixel_search_batch: obmc_full_pixel_search_batch
+    over int16 / uint16 reference planes (ref_stride in elements)."""
+    import torch
+    _hbd_planes(ref, ref)
+    nj = jobs.numel() // COMP_JOB_DTYPE.itemsize
+    out = _comp_out(nj, out, ref.device)
+    rc = _lib.lavish_highbd_obmc_full_pixel_search_batch(
+        _vp(ref.data_ptr()), ref_stride, w, h, bit_depth, _vp(jobs.data_ptr()), nj,
+        SEARCH_METHODS[method], step_param, ctypes.byref(cost), int(fast_obmc_search),
+        _ptr(wsrc, torch.int32), _ptr(obmc_mask, torch.int32), _vp(out.data_ptr()),
+        _stream_ptr(stream))
+    if rc != 0:
+        raise ValueError("lavish_highbd_obmc_full_pixel_search_batch rejected its arguments "
+                         "(rc=%d)" % rc)
+    return out
+
+
+def highbd_comp_find_best_sub_pixel_tree_batch(src, ref, w, h, jobs, cost, second_pred, mask=None,
+                                               mask_stride=0, bit_depth=10, method="pruned_more",
+                                               forced_stop=EIGHTH_PEL, allow_hp=False,
+                                               iters_per_step=1, fullpel=None, start_from=0,
+                                               out=None, stream=None):
+    """lavish_highbd_comp_find_best_sub_pixel_tree_batch:
+    comp_find_best_sub_pixel_tree_batch (the bilinear error) over int16 /
+    uint16 planes; fullpel: the bytes one of the highbd compound full-pel calls
+    returned, still on the device."""
+    import torch
+    _hbd_planes(src, ref)
+    nj = jobs.numel() // COMP_SUBPEL_JOB_DTYPE.itemsize
+    if fullpel is not None:
+        assert fullpel.numel() >= nj * COMP_RESULT_DTYPE.itemsize
+    out = _subpel_out(nj, out, src.device)
+    rc = _lib.lavish_highbd_comp_find_best_sub_pixel_tree_batch(
+        _vp(src.data_ptr()), src.stride(0), _vp(ref.data_ptr()), src.stride(0), w, h, bit_depth,
+        _vp(jobs.data_ptr()), None if fullpel is None else _vp(fullpel.data_ptr()), start_from,
+        nj, SUBPEL_METHODS[method], forced_stop, int(allow_hp), iters_per_step,
+        ctypes.byref(cost), _ptr16(second_pred), _ptr(mask, torch.uint8), mask_stride,
+        _vp(out.data_ptr()), _stream_ptr(stream))
+    if rc != 0:
+        raise ValueError("lavish_highbd_comp_find_best_sub_pixel_tree_batch rejected its "
+                         "arguments (rc=%d)" % rc)
+    return out
+
+
+def highbd_obmc_find_best_sub_pixel_tree_batch(ref, ref_stride, w, h, jobs, cost, wsrc, obmc_mask,
+                                               bit_depth=10, forced_stop=EIGHTH_PEL,
+                                               allow_hp=False, iters_per_step=1, fullpel=None,
+                                               out=None, stream=None):
+    """lavish_highbd_obmc_find_best_sub_pixel_tree_batch:
+    obmc_find_best_sub_pixel_tree_batch with USE_2_TAPS_ORIG over int16 /
+    uint16 reference planes."""
+    import torch
+    _hbd_planes(ref, ref)
+    nj = jobs.numel() // COMP_SUBPEL_JOB_DTYPE.itemsize
+    if fullpel is not None:
+        assert fullpel.numel() >= nj * COMP_RESULT_DTYPE.itemsize
+    out = _subpel_out(nj, out, ref.device)
+    rc = _lib.lavish_highbd_obmc_find_best_sub_pixel_tree_batch(
+        _vp(ref.data_ptr()), ref_stride, w, h, bit_depth, _vp(jobs.data_ptr()),
+        None if fullpel is None else _vp(fullpel.data_ptr()), nj, forced_stop, int(allow_hp),
+        iters_per_step, ctypes.byref(cost), _ptr(wsrc, torch.int32),
+        _ptr(obmc_mask, torch.int32), _vp(out.data_ptr()), _stream_ptr(stream))
+    if rc != 0:
+        raise ValueError("lavish_highbd_obmc_find_best_sub_pixel_tree_batch rejected its "
+                         "arguments (rc=%d)" % rc)
+    return out

@@ -1235,6 +1235,72 @@ int lavish_obmc_find_best_sub_pixel_tree_batch(
     int allow_hp, int iters_per_step, const LavishMvCostParams *cost, const int32_t *wsrc,
     const int32_t *obmc_mask, LavishSubpelResult *out, void *stream);
 
+/* ---- high bit depth: the compound, masked and OBMC searches ---------------
+ * The five calls above (lavish_comp_full_pixel_search_batch,
+ * lavish_refining_search_8p_batch, lavish_obmc_full_pixel_search_batch,
+ * lavish_comp_find_best_sub_pixel_tree_batch and
+ * lavish_obmc_find_best_sub_pixel_tree_batch) over uint16_t planes holding
+ * bit_depth-bit pixels (8, 10 or 12), csrc/mcomp_comp_hbd.hip and
+ * csrc/subpel_comp_hbd.hip, one wave per job, with the members
+ * highbd_set_var_fns binds (av1/encoder/encoder_utils.h): sdaf =
+ * aom_highbd_sad{W}x{H}_avg, msdf = aom_highbd_masked_sad{W}x{H}, osdf =
+ * aom_highbd_obmc_sad{W}x{H} under their _bits8 / _bits10 / _bits12 wrappers
+ * (the whole block's SAD >> 0 / 2 / 4, before the mv SAD cost is added);
+ * svaf = aom_highbd_{8,10,12}_sub_pixel_avg_variance{W}x{H}, msvf =
+ * aom_highbd_{8,10,12}_masked_sub_pixel_variance{W}x{H}, ovf / osvf =
+ * aom_highbd_[10_|12_]obmc_[sub_pixel_]variance{W}x{H}; setup_center_error
+ * through aom_highbd_comp_avg_pred / aom_highbd_comp_mask_pred and vf.
+ * Jobs and results are the 8-bit calls' records.  src_stride, ref_stride and
+ * the jobs' src_off / ref_off are in ELEMENTS (uint16_t); second_pred is
+ * uint16_t (compact blocks, stride w, second_off in elements); mask stays
+ * uint8_t with mask_stride, wsrc / obmc_mask int32_t.  Everything else --
+ * the searches, second_best_mv, fullpel chaining with start_from 0 / 1 and
+ * its INT_MAX / -32768 record, the three OBMC sub-pel peculiarities -- is the
+ * 8-bit twin's.  The sub-pel calls take no subpel_search_type: the error is
+ * the bilinear one (USE_2_TAPS_ORIG), as in
+ * lavish_highbd_find_best_sub_pixel_tree_batch.
+ * Padding: as the 8-bit twins, in elements: exactly the w x h blocks (full
+ * pel) or the (w + 1) x (h + 1) windows (sub pel) the reference reads.
+ * Return codes are the twins', and a bit_depth outside {8, 10, 12} returns
+ * -7 (full pel) or -8 (sub pel); every refusal comes before any device work
+ * and leaves out untouched; njobs <= 0 returns 0. */
+int lavish_highbd_comp_full_pixel_search_batch(
+    const uint16_t *src, int src_stride, const uint16_t *ref, int ref_stride,
+    int w, int h, int bit_depth, const LavishCompSearchJob *jobs, int njobs,
+    int search_method, int step_param, const LavishMvCostParams *cost,
+    const uint16_t *second_pred, const uint8_t *mask, int mask_stride,
+    LavishCompSearchResult *out, void *stream);
+
+int lavish_highbd_refining_search_8p_batch(
+    const uint16_t *src, int src_stride, const uint16_t *ref, int ref_stride,
+    int w, int h, int bit_depth, const LavishCompSearchJob *jobs, int njobs,
+    const LavishMvCostParams *cost, const uint16_t *second_pred,
+    const uint8_t *mask, int mask_stride, LavishCompSearchResult *out,
+    void *stream);
+
+int lavish_highbd_obmc_full_pixel_search_batch(
+    const uint16_t *ref, int ref_stride, int w, int h, int bit_depth,
+    const LavishCompSearchJob *jobs, int njobs, int search_method,
+    int step_param, const LavishMvCostParams *cost, int fast_obmc_search,
+    const int32_t *wsrc, const int32_t *obmc_mask, LavishCompSearchResult *out,
+    void *stream);
+
+int lavish_highbd_comp_find_best_sub_pixel_tree_batch(
+    const uint16_t *src, int src_stride, const uint16_t *ref, int ref_stride,
+    int w, int h, int bit_depth, const LavishCompSubpelJob *jobs,
+    const LavishCompSearchResult *fullpel, int start_from, int njobs,
+    int subpel_search_method, int forced_stop, int allow_hp,
+    int iters_per_step, const LavishMvCostParams *cost,
+    const uint16_t *second_pred, const uint8_t *mask, int mask_stride,
+    LavishSubpelResult *out, void *stream);
+
+int lavish_highbd_obmc_find_best_sub_pixel_tree_batch(
+    const uint16_t *ref, int ref_stride, int w, int h, int bit_depth,
+    const LavishCompSubpelJob *jobs, const LavishCompSearchResult *fullpel,
+    int njobs, int forced_stop, int allow_hp, int iters_per_step,
+    const LavishMvCostParams *cost, const int32_t *wsrc,
+    const int32_t *obmc_mask, LavishSubpelResult *out, void *stream);
+
 /* ---- Inter prediction -----------------------------
  * av1_enc_build_one_inter_predictor (av1/encoder/reconinter_enc.c:47-51) for
  * a batch of single-reference translational blocks: init_subpel_params
