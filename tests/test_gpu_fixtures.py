@@ -8,6 +8,9 @@ import os
 import numpy as np
 import pytest
 
+pytest.register_assert_rewrite("_shimcases")
+import _shimcases as S  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -73,16 +76,10 @@ def test_fwd_batch_vs_reference(L, FT, s):
 def test_fwd_shims_vs_reference(L, FT, s):
     """av1_fwd_txfm2d_{WxH}_hip: the whole W*H output buffer the reference
     writes (64-point sizes: zeroed + re-packed in place)."""
-    W, H = TX_W[s], TX_H[s]
-    fn = getattr(L, "av1_fwd_txfm2d_" + L.TX_SIZES[s])
-    for t in _types(L, s):
-        for blk, exp, bd in zip(FT["in_%d_%d" % (s, t)], FT["out_%d_%d" % (s, t)],
-                                FT["bd_%d_%d" % (s, t)]):
-            padded = np.zeros((H, W + 3), np.int16)
-            padded[:, :W] = blk
-            got = np.full(W * H, 0x5A5A5A5A, np.int32)
-            fn(padded, got, W + 3, t, int(bd))
-            np.testing.assert_array_equal(got, exp, err_msg="size %d type %d" % (s, t))
+    cases = list(S.fwd_shim_cases(L, FT, s))
+    assert len(cases) == sum(len(FT["in_%d_%d" % (s, t)]) for t in _types(L, s)) > 0
+    for _label, run in cases:
+        run()
 
 
 def _qp(L, F, bd, q, kind):
@@ -97,10 +94,7 @@ def _qp(L, F, bd, q, kind):
     return qp
 
 
-def _quant_cases(FQ):
-    for ci, (s, ls, hb, isb) in enumerate(FQ["cases"]):
-        for q in (0, 32, 128, 255):
-            yield ci, int(s), int(ls), bool(hb), bool(isb), 10 if hb else 8, q
+_quant_cases = S.quant_grid
 
 
 def test_quantize_batch_vs_reference(L, FQ):
@@ -128,28 +122,11 @@ def test_quantize_batch_vs_reference(L, FQ):
 def test_quantize_shims_vs_reference(L, FQ):
     """The per-call RTCD shims named like the reference's functions
     (av1_quantize_fp_hip, aom_quantize_b_32x32_hip, ...)."""
-    G = _load("fix_qparams.npz")
-    for ci, s, ls, hb, isb, bd, q in _quant_cases(FQ):
-        name = str(FQ["case_names"][ci])[:-2]  # drop "_c"
-        key = "%d_%d_q%d" % (ci, bd, q)
-        n = L.max_eob(s)
-        scan, iscan = L.scan_order(s, 0)
-        row = lambda f: np.ascontiguousarray(G["%s_bd%d_sh0" % (f, bd)][q])
-        rnd, qnt = (row("y_round"), row("y_quant")) if isb else (row("y_round_fp"),
-                                                                  row("y_quant_fp"))
-        for k, c in enumerate(FQ["coeff_" + key]):
-            qc = np.full(n, 99, np.int32)
-            dq = np.full(n, 99, np.int32)
-            eob = np.zeros(1, np.uint16)
-            args = [np.ascontiguousarray(c), n, row("y_zbin"), rnd, qnt, row("y_quant_shift"), qc,
-                    dq, row("y_dequant_QTX"), eob, scan, iscan]
-            if name == "av1_highbd_quantize_fp":
-                args.append(ls)
-            getattr(L, name)(*args)
-            msg = "%s q %d block %d" % (name, q, k)
-            np.testing.assert_array_equal(qc, FQ["qcoeff_" + key][k], err_msg=msg)
-            np.testing.assert_array_equal(dq, FQ["dqcoeff_" + key][k], err_msg=msg)
-            assert eob[0] == FQ["eob_" + key][k], msg
+    cases = list(S.quant_shim_cases(L, FQ, _load("fix_qparams.npz")))
+    assert len(cases) == sum(len(FQ["coeff_%d_%d_q%d" % (c[0], c[5], c[6])])
+                             for c in _quant_cases(FQ)) > 300
+    for _label, run in cases:
+        run()
 
 
 @pytest.mark.parametrize("s", range(19))
@@ -184,20 +161,15 @@ def test_inv_batch_vs_reference(L, FI, s):
 def test_inv_shims_vs_reference(L, FI, s):
     """av1_inv_txfm2d_add_{WxH}_hip on the fixture's u16 destination (stride
     W + 5, only the W x H window may change)."""
-    for t in _types(L, s):
-        key = "%d_%d" % (s, t)
-        for c, dst, exp, bd in zip(FI["in_" + key], FI["dst_" + key], FI["out_" + key],
-                                   FI["bd_" + key]):
-            d = dst.copy()
-            L.av1_inv_txfm2d_add(s, np.ascontiguousarray(c), d, d.shape[1], t, int(bd))
-            np.testing.assert_array_equal(d, exp, err_msg="size %d type %d bd %d" % (s, t, bd))
+    cases = list(S.inv_shim_cases(L, FI, s))
+    assert len(cases) == sum(len(FI["in_%d_%d" % (s, t)]) for t in _types(L, s)) > 0
+    for _label, run in cases:
+        run()
 
 
 # ---------------------------------------------------------------- pixel --
-BLOCK_SIZES = [(128, 128), (128, 64), (64, 128), (64, 64), (64, 32), (32, 64), (32, 32), (32, 16),
-               (16, 32), (16, 16), (16, 8), (8, 16), (8, 8), (8, 4), (4, 8), (4, 4), (4, 16),
-               (16, 4), (8, 32), (32, 8), (16, 64), (64, 16)]
-SUBPEL_OFFSETS = [(0, 0), (3, 0), (0, 5), (4, 4), (7, 2)]
+BLOCK_SIZES = S.BLOCK_SIZES
+SUBPEL_OFFSETS = S.SUBPEL_OFFSETS
 
 
 @pytest.fixture(scope="module")
@@ -214,19 +186,7 @@ def PX():
 @pytest.mark.parametrize("W,H", BLOCK_SIZES)
 @pytest.mark.parametrize("bd", [8, 10])
 def test_sad_variance_shims_vs_reference(L, PX, FP, W, H, bd):
-    k = "%dx%d_bd%d" % (W, H, bd)
-    dt = np.uint8 if bd == 8 else np.uint16
-    a, b = FP["src_" + k].astype(dt), FP["ref_" + k].astype(dt)
-    hb = bd > 8
-    ss, rs = a.shape[1], b.shape[1]
-    assert PX.sad(W, H, a, ss, b, rs, highbd=hb) == FP["sad_" + k][0]
-    assert PX.sad(W, H, a, ss, b, rs, highbd=hb, skip=True) == FP["sadskip_" + k][0]
-    flat = b.reshape(-1)
-    got4 = PX.sad_x4d(W, H, a, ss, [flat[o:] for o in (0, 1, 3, W + 2)], rs, highbd=hb)
-    np.testing.assert_array_equal(got4, FP["sadx4d_" + k])
-    assert list(PX.variance(W, H, a, ss, b, rs, bd, hb)) == list(FP["var_" + k])
-    got = [PX.sub_pixel_variance(W, H, a, ss, xo, yo, b, rs, bd, hb) for xo, yo in SUBPEL_OFFSETS]
-    np.testing.assert_array_equal(np.array(got, np.int64), FP["subvar_" + k])
+    S.sad_variance_shim_case(PX, FP, W, H, bd)[1]()
 
 
 @pytest.mark.parametrize("bd", [8, 10])
@@ -292,23 +252,10 @@ def test_block_error_lp_vs_reference(L, PX, FP):
 
 
 def test_subtract_sse_sums_vs_reference(L, PX, FP):
-    for (w, h) in ((4, 4), (8, 4), (16, 16), (7, 5), (64, 64), (32, 8), (128, 128)):
+    assert S.SUBTRACT_SIZES == ((4, 4), (8, 4), (16, 16), (7, 5), (64, 64), (32, 8), (128, 128))
+    for (w, h) in S.SUBTRACT_SIZES:
         for bd in (8, 10):
-            k = "%dx%d_bd%d" % (w, h, bd)
-            dt = np.uint8 if bd == 8 else np.uint16
-            src, prd = FP["s_src_" + k].astype(dt), FP["s_pred_" + k].astype(dt)
-            exp = FP["sub_" + k]
-            diff = np.full(exp.shape, 0x7777, np.int16)
-            PX.subtract_block(h, w, diff, diff.shape[1], src, src.shape[1], prd, prd.shape[1],
-                              highbd=bd > 8)
-            np.testing.assert_array_equal(diff, exp, err_msg=k)
-            assert PX.sse(src, src.shape[1], prd, prd.shape[1], w, h, highbd=bd > 8) == \
-                FP["sse_" + k][0]
-            assert PX.sum_squares_2d_i16(exp, exp.shape[1], w, h) == FP["sumsq_" + k][0]
-            # the caller's *sum is accumulated into, as the reference does
-            ss, sm = PX.sum_sse_2d_i16(exp, exp.shape[1], w, h, sum_in=7)
-            assert [ss, sm - 7] == list(FP["sumsse_" + k])
-            assert list(PX.get_blk_sse_sum(exp, exp.shape[1], w, h)) == list(FP["blksse_" + k])
+            S.subtract_sse_shim_case(PX, FP, w, h, bd)[1]()
 
 
 def test_wht_vs_reference(L, PX):

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 
 import _oracle as O
+pytest.register_assert_rewrite("_shimcases")
+import _shimcases as S  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -26,15 +28,7 @@ def Wp():
     return Wp
 
 
-def _case(F, r, J):
-    g = lambda k: int(r[J[k]])
-    W, H, RS, PS, DS = (int(v) for v in F["geom"])
-    bd = g("bd")
-    mode = g("mode")
-    cp = dict(round_0=g("round_0"), round_1=g("round_1"), is_compound=int(mode > 0),
-              do_average=int(mode >= 2), dist_wtd=int(mode == 3), fwd_offset=g("fwd_offset"),
-              bck_offset=g("bck_offset"))
-    return g, W, H, RS, PS, DS, bd, cp
+_case = S.warp_row
 
 
 def test_warp_batch_vs_reference(Wp):
@@ -67,21 +61,10 @@ def test_warp_batch_vs_reference(Wp):
 
 def test_warp_shims_vs_reference(Wp):
     F = dict(np.load(os.path.join(GOLD, "fix_warp.npz")))
-    J = {n: i for i, n in enumerate(F["row_fields"])}
-    for k, r in enumerate(F["rows"]):
-        if k % 3:
-            continue
-        g, W, H, RS, PS, DS, bd, cp = _case(F, r, J)
-        pdt = np.uint16 if bd > 8 else np.uint8
-        ref = np.ascontiguousarray(F["refs"][g("ref_index")].astype(pdt))
-        pred = F["pred_in"][k].astype(pdt).copy()
-        dst = F["dst_in"][k].copy()
-        c = Wp.conv_params(dst=dst, dst_stride=DS, **cp)
-        Wp.warp_affine_shim([g("m%d" % i) for i in range(6)], ref, W, H, RS, pred, g("p_col"),
-                            g("p_row"), g("p_width"), g("p_height"), PS, g("ss_x"), g("ss_y"), c,
-                            tuple(g(f) for f in ("alpha", "beta", "gamma", "delta")), bd)
-        np.testing.assert_array_equal(pred.astype(np.uint16), F["pred"][k], err_msg="row %d" % k)
-        np.testing.assert_array_equal(dst, F["dst"][k], err_msg="row %d dst" % k)
+    cases = list(S.warp_shim_cases(Wp, F))
+    assert len(cases) == (len(F["rows"]) + 2) // 3 > 0
+    for _label, run in cases:
+        run()
 
 
 def _models(rng, n):
