@@ -15,6 +15,9 @@ int txq_plane(const int16_t*, int, int, int, int, uint32_t, int, int, const Lavi
               int32_t*, int32_t*, uint16_t*, int32_t*, hipStream_t);
 int quantize_batch(const int32_t*, int, int, const int16_t*, int, int, int,
                    const LavishQuantParams*, int32_t*, int32_t*, uint16_t*, hipStream_t);
+int quantize_qm_batch(const int32_t*, int, int, const int16_t*, int, int, int,
+                      const LavishQuantParams*, const uint8_t*, const uint8_t*, int32_t*, int32_t*,
+                      uint16_t*, hipStream_t);
 
 // ---------------------------------------------------------------- status --
 static int g_status = 0;
@@ -469,6 +472,43 @@ QUANT_SHIM(aom_highbd_quantize_b_hip, 0, LAVISH_QUANT_B, 10)
 QUANT_SHIM(aom_highbd_quantize_b_32x32_hip, 1, LAVISH_QUANT_B, 10)
 QUANT_SHIM(aom_highbd_quantize_b_64x64_hip, 2, LAVISH_QUANT_B, 10)
 #undef QUANT_SHIM
+
+// aom_quantize_b_helper (av1/common/av1_rtcd_defs.pl:346; aom_dsp/quantize.c:
+// 108-169): the low-bit-depth B quantizer with nullable matrices
+void aom_quantize_b_helper_hip(const int32_t* coeff_ptr, intptr_t n_coeffs,
+                               const int16_t* zbin_ptr, const int16_t* round_ptr,
+                               const int16_t* quant_ptr, const int16_t* quant_shift_ptr,
+                               int32_t* qcoeff_ptr, int32_t* dqcoeff_ptr,
+                               const int16_t* dequant_ptr, uint16_t* eob_ptr, const int16_t* scan,
+                               const int16_t* iscan, const uint8_t* qm_ptr, const uint8_t* iqm_ptr,
+                               const int log_scale) {
+  (void)iscan;
+  const size_t n = (size_t)n_coeffs;
+  LavishQuantParams qp;
+  for (int i = 0; i < 2; ++i) {
+    qp.zbin[i] = zbin_ptr[i];
+    qp.round[i] = round_ptr[i];
+    qp.quant[i] = quant_ptr[i];
+    qp.quant_shift[i] = quant_shift_ptr[i];
+    qp.dequant[i] = dequant_ptr[i];
+  }
+  Stage st(3 * Stage::pad(n * sizeof(int32_t)) + Stage::pad(n * sizeof(int16_t)) +
+           2 * Stage::pad(n) + Stage::pad(sizeof(uint16_t)));
+  const int32_t* dc = st.copy_in(coeff_ptr, n);
+  int32_t* dq = st.take_n<int32_t>(n);
+  int32_t* ddq = st.take_n<int32_t>(n);
+  const int16_t* dscan = st.copy_in(scan, n);
+  const uint8_t* dqm = qm_ptr ? st.copy_in(qm_ptr, n) : nullptr;
+  const uint8_t* diqm = iqm_ptr ? st.copy_in(iqm_ptr, n) : nullptr;
+  uint16_t* deob = st.take_n<uint16_t>(1);
+  must(quantize_qm_batch(dc, (int)n, 1, dscan, log_scale, 8, LAVISH_QUANT_B, &qp, dqm, diqm, dq,
+                         ddq, deob, st.s),
+       "aom_quantize_b_helper");
+  st.copy_out(qcoeff_ptr, dq, n);
+  st.copy_out(dqcoeff_ptr, ddq, n);
+  st.copy_out(eob_ptr, deob, 1);
+  st.sync();
+}
 
 void av1_highbd_quantize_fp_hip(const int32_t* coeff_ptr, intptr_t count,
                                 const int16_t* zbin_ptr, const int16_t* round_ptr,

@@ -2,8 +2,13 @@
 // gfx950.
 //
 // Reference: av1_optimize_b (av1/encoder/encodemb.c:87-103) ->
-// av1_optimize_txb (av1/encoder/txb_rdopt.c:326-449), no quantization
-// matrix (the default PSNR metric; a flat iqmatrix changes nothing):
+// av1_optimize_txb (av1/encoder/txb_rdopt.c:326-449).  The flat instantiation
+// (QM false, lavish_optimize_b_batch): no quantization matrix, the default
+// PSNR metric.  The matrix instantiation (QM true, lavish_optimize_b_qm_batch):
+// get_dqv weights the dequantizer by iqmatrix[ci] and, under
+// AOM_DIST_METRIC_QM_PSNR, get_coeff_dist weights the difference by
+// qmatrix[ci] (txb_rdopt_utils.h:39-64, txb_rdopt.c:309-313); either may be
+// NULL.  The walk:
 //   rdmult = (x->rdmult * (plane_rd_mult[is_inter][plane_type] << 2(bd-8))
 //             + 2) >> (sharpness + 2);
 //   the last coefficient: update_coeff_general (|q| >= 2) or its eob cost;
@@ -22,8 +27,11 @@
 // |level| map (av1_txb_init_levels layout) lives in LDS; the block's
 // LV_MAP_COEFF_COST / LV_MAP_EOB_COST and the scan are staged in LDS once per
 // workgroup; coefficients are read / rewritten in place in global memory.
+#include <type_traits>
+
 #include "coeffcost_dev.h"
 #include "lavish_internal.h"
+#include "quant_qm_dev.h"
 
 namespace lavish {
 namespace {
@@ -45,8 +53,19 @@ struct TrArgs {
   int nblocks, n, w, h, bhl, cls, wlt, wgt, shift, sharpness;
   int dqv_dc, dqv_ac, tx_type_cost, non_skip_plane;
 };
+// the matrix instantiation's arguments; the flat kernel keeps TrArgs as it is
+struct TrArgsQm : TrArgs {
+  const uint8_t* iqm;  // get_dqv's iqmatrix, n entries, nullable
+  const uint8_t* qmd;  // get_coeff_dist's qmatrix (QM-PSNR), n entries, nullable
+};
+struct NoQm {};
+struct QmTabs {
+  const uint8_t* iqm;
+  const uint8_t* qmd;
+};
 
 // the lane's walk state and the block-invariant context
+template <bool QM>
 struct Walk {
   const int32_t* tab;  // LDS: cost cells, then the eob cells
   const int16_t* scan; // LDS
@@ -57,13 +76,18 @@ struct Walk {
   int64_t rdmult;
   int n, h, bhl, stride, cls, wlt, wgt, shift, sharpness, dqv_dc, dqv_ac, dc_sign_ctx;
   NbrOff nb;  // the class's neighbour offsets in the level map
+  [[no_unique_address]] std::conditional_t<QM, QmTabs, NoQm> m;
 
   // RDCOST (av1/encoder/rd.h:31-33)
   __device__ __forceinline__ int64_t rd(int64_t r, int64_t d) const {
     return ((r * rdmult + 256) >> 9) + d * 128;
   }
-  // get_coeff_dist without a qmatrix (txb_rdopt_utils.h:48-66)
-  __device__ __forceinline__ int64_t dist(int32_t t, int32_t d) const {
+  // get_coeff_dist (txb_rdopt_utils.h:48-66); QM: weighted when the QM-PSNR
+  // matrix is set
+  __device__ __forceinline__ int64_t dist(int32_t t, int32_t d, int ci) const {
+    if constexpr (QM) {
+      if (m.qmd) return qm::coeff_dist_qm(t, d, shift, m.qmd[ci]);
+    }
     const int64_t x = (int32_t)((t - d) * (1 << shift));
     return x * x;
   }
@@ -112,7 +136,14 @@ struct Walk {
     }
     return c;
   }
-  __device__ __forceinline__ int dqv(int ci) const { return ci ? dqv_ac : dqv_dc; }
+  // get_dqv (txb_rdopt_utils.h:39-46)
+  __device__ __forceinline__ int dqv(int ci) const {
+    const int d = ci ? dqv_ac : dqv_dc;
+    if constexpr (QM) {
+      if (m.iqm) return qm::weighted_dequant(d, m.iqm[ci]);
+    }
+    return d;
+  }
 
   // update_coeff_general (txb_rdopt.c:17-73)
   __device__ __forceinline__ void general(int& accu_rate, int64_t& accu_dist, int si, int eob) const {
@@ -126,7 +157,7 @@ struct Walk {
     }
     const int sign = q < 0, a = abs(q);
     const int32_t t = tc[ci];
-    const int64_t d = dist(t, dqc[ci]), d0 = dist(t, 0);
+    const int64_t d = dist(t, dqc[ci], ci), d0 = dist(t, 0, ci);
     const int r = cost_general(last, ci, a, sign, ctx);
     int32_t ql = 0, dql = 0;
     int al = 0, rl;
@@ -139,7 +170,7 @@ struct Walk {
       const int32_t adl = (al * dqv(ci)) >> shift;
       ql = sign ? -al : al;
       dql = sign ? -adl : adl;
-      dl = dist(t, dql);
+      dl = dist(t, dql, ci);
       rl = cost_general(last, ci, al, sign, ctx);
     }
     if (rd(rl, dl) < rd(r, d)) {
@@ -185,7 +216,7 @@ struct Walk {
     }
     const int al = a - 1;
     const int32_t adl = (al * dqv(ci)) >> shift;
-    if (rd(cost - diff, dist(at, adl)) < rd(cost, dist(at, adq))) {
+    if (rd(cost - diff, dist(at, adl, ci)) < rd(cost, dist(at, adq, ci))) {
       const int sign = q < 0;
       qc[ci] = sign ? -al : al;
       dqc[ci] = sign ? -adl : adl;
@@ -208,8 +239,8 @@ struct Walk {
     }
     const int a = abs(q), sign = q < 0;
     const int32_t t = tc[ci];
-    const int64_t d0 = dist(t, 0);
-    int64_t d = dist(t, dqc[ci]) - d0;
+    const int64_t d0 = dist(t, 0, ci);
+    int64_t d = dist(t, dqc[ci], ci) - d0;
     int r = cost_general(false, ci, a, sign, ctx);
     int64_t cur = rd(accu_rate + r, accu_dist + d);
     int32_t ql = 0, dql = 0;
@@ -224,7 +255,7 @@ struct Walk {
       const int32_t adl = (al * dqv(ci)) >> shift;
       ql = sign ? -al : al;
       dql = sign ? -adl : adl;
-      dl = dist(t, dql) - d0;
+      dl = dist(t, dql, ci) - d0;
       rl = cost_general(false, ci, al, sign, ctx);
       rdl = rd(accu_rate + rl, accu_dist + dl);
     }
@@ -284,8 +315,8 @@ struct Walk {
   }
 };
 
-template <int N>
-__global__ __launch_bounds__(64) void trellis_kernel(TrArgs a) {
+template <int N, bool QM = false>
+__global__ __launch_bounds__(64) void trellis_kernel(std::conditional_t<QM, TrArgsQm, TrArgs> a) {
   constexpr int BPW = N >= 1024 ? 32 : 64;  // blocks (lanes) per wave: LDS <= 48 KB
   // max (w + 4) * (h + 4) over the adjusted sizes with w * h = N
   constexpr int LVB = N == 16 ? 64 : N == 32 ? 96 : N == 64 ? 160 : N == 128 ? 240
@@ -297,11 +328,26 @@ __global__ __launch_bounds__(64) void trellis_kernel(TrArgs a) {
   for (int i = lane; i < kCostCells; i += 64) tab[i] = a.cost[i];
   if (lane < kEobCells) tab[kCostCells + lane] = a.eobc[lane];
   for (int i = lane; i < N; i += 64) scan[i] = a.scan[i];
+  Walk<QM> w;
+  if constexpr (QM) {
+    w.m.iqm = a.iqm;
+    w.m.qmd = a.qmd;
+    // beside the 32 level maps of N = 1024 two more KB do not fit the 48 KB:
+    // there the lanes gather the bytes through the cache
+    if constexpr (N < 1024) {
+      __shared__ uint8_t mats[2 * N];
+      for (int i = lane; i < N; i += 64) {
+        mats[i] = a.iqm ? a.iqm[i] : 0;
+        mats[N + i] = a.qmd ? a.qmd[i] : 0;
+      }
+      if (a.iqm) w.m.iqm = mats;
+      if (a.qmd) w.m.qmd = mats + N;
+    }
+  }
   __syncthreads();
   const int b = blockIdx.x * BPW + lane;
   if (lane >= BPW || b >= a.nblocks) return;
 
-  Walk w;
   w.tab = tab;
   w.scan = scan;
   w.lv = lvs + lane * LVB;
@@ -349,7 +395,7 @@ __global__ __launch_bounds__(64) void trellis_kernel(TrArgs a) {
       w.general(accu_rate, accu_dist, si, eob);
     } else {
       accu_rate += w.cost_eob(ci, abs(q), q < 0, w.eob_ctx(si));
-      accu_dist += w.dist(w.tc[ci], w.dqc[ci]) - w.dist(w.tc[ci], 0);
+      accu_dist += w.dist(w.tc[ci], w.dqc[ci], ci) - w.dist(w.tc[ci], 0, ci);
     }
   }
   int nz_num = 1, nz0 = scan[si], nz1 = 0, nz2 = 0;
@@ -395,13 +441,13 @@ int ilog2i(int v) { return 31 - __builtin_clz(v); }
 
 using namespace lavish;
 
-extern "C" int lavish_optimize_b_batch(const LavishCoeffCosts* costs, const int32_t* tcoeff,
-                                       int32_t* qcoeff, int32_t* dqcoeff, uint16_t* eob,
-                                       int nblocks, int plane, int tx_size, int tx_type,
-                                       int bit_depth, int is_inter, int rdmult, int sharpness,
-                                       const int16_t* dequant, const LavishTxbCtx* txb_ctx,
-                                       int tx_type_cost, int32_t* rate, uint8_t* entropy_ctx,
-                                       void* stream) {
+// both entry points; iqm / qmd already nulled for the flat types
+static int optimize_b(const LavishCoeffCosts* costs, const int32_t* tcoeff, int32_t* qcoeff,
+                      int32_t* dqcoeff, uint16_t* eob, int nblocks, int plane, int tx_size,
+                      int tx_type, int bit_depth, int is_inter, int rdmult, int sharpness,
+                      const int16_t* dequant, const uint8_t* iqm, const uint8_t* qmd,
+                      const LavishTxbCtx* txb_ctx, int tx_type_cost, int32_t* rate,
+                      uint8_t* entropy_ctx, void* stream) {
   if (tx_size < 0 || tx_size >= 19 || tx_type < 0 || tx_type >= 16) return -1;
   if (plane < 0 || plane > 2 || (is_inter != 0 && is_inter != 1)) return -2;
   if (costs == nullptr || tcoeff == nullptr || qcoeff == nullptr || dqcoeff == nullptr ||
@@ -416,7 +462,9 @@ extern "C" int lavish_optimize_b_batch(const LavishCoeffCosts* costs, const int3
   const int mn = txw < txh ? txw : txh, mx = txw < txh ? txh : txw;
   const int txs_ctx = (ilog2i(mn) - 2 + ilog2i(mx) - 2 + 1) >> 1;  // get_txsize_entropy_ctx
   const int pt = plane > 0;
-  TrArgs a{};
+  TrArgsQm a{};
+  a.iqm = iqm;
+  a.qmd = qmd;
   a.cost = &costs->coeff_costs[txs_ctx][pt].txb_skip_cost[0][0];
   a.eobc = &costs->eob_costs[ilog2i(w * h) - 4][pt].eob_cost[0][0];
   a.tcoeff = tcoeff;
@@ -445,8 +493,12 @@ extern "C" int lavish_optimize_b_batch(const LavishCoeffCosts* costs, const int3
   hipStream_t s = (hipStream_t)stream;
   const int bpw = a.n >= 1024 ? 32 : 64;
   const int grid = (nblocks + bpw - 1) / bpw;
-#define LAVISH_TR(NN) \
-  case NN: hipLaunchKernelGGL((trellis_kernel<NN>), dim3(grid), dim3(64), 0, s, a); break;
+  const bool with_qm = iqm != nullptr || qmd != nullptr;
+#define LAVISH_TR(NN)                                                                          \
+  case NN:                                                                                     \
+    if (with_qm) hipLaunchKernelGGL((trellis_kernel<NN, true>), dim3(grid), dim3(64), 0, s, a); \
+    else hipLaunchKernelGGL((trellis_kernel<NN>), dim3(grid), dim3(64), 0, s, (TrArgs)a);      \
+    break;
   switch (a.n) {
     LAVISH_TR(16)
     LAVISH_TR(32)
@@ -460,4 +512,31 @@ extern "C" int lavish_optimize_b_batch(const LavishCoeffCosts* costs, const int3
 #undef LAVISH_TR
   LAVISH_CHECK(hipGetLastError());
   return 0;
+}
+
+extern "C" int lavish_optimize_b_batch(const LavishCoeffCosts* costs, const int32_t* tcoeff,
+                                       int32_t* qcoeff, int32_t* dqcoeff, uint16_t* eob,
+                                       int nblocks, int plane, int tx_size, int tx_type,
+                                       int bit_depth, int is_inter, int rdmult, int sharpness,
+                                       const int16_t* dequant, const LavishTxbCtx* txb_ctx,
+                                       int tx_type_cost, int32_t* rate, uint8_t* entropy_ctx,
+                                       void* stream) {
+  return optimize_b(costs, tcoeff, qcoeff, dqcoeff, eob, nblocks, plane, tx_size, tx_type,
+                    bit_depth, is_inter, rdmult, sharpness, dequant, nullptr, nullptr, txb_ctx,
+                    tx_type_cost, rate, entropy_ctx, stream);
+}
+
+extern "C" int lavish_optimize_b_qm_batch(const LavishCoeffCosts* costs, const int32_t* tcoeff,
+                                          int32_t* qcoeff, int32_t* dqcoeff, uint16_t* eob,
+                                          int nblocks, int plane, int tx_size, int tx_type,
+                                          int bit_depth, int is_inter, int rdmult, int sharpness,
+                                          const int16_t* dequant, const uint8_t* iqm,
+                                          const uint8_t* qm_dist, const LavishTxbCtx* txb_ctx,
+                                          int tx_type_cost, int32_t* rate, uint8_t* entropy_ctx,
+                                          void* stream) {
+  const bool flat_type = tx_type >= 9;  // av1_get_iqmatrix / av1_get_qmatrix: 1-D and identity
+  return optimize_b(costs, tcoeff, qcoeff, dqcoeff, eob, nblocks, plane, tx_size, tx_type,
+                    bit_depth, is_inter, rdmult, sharpness, dequant, flat_type ? nullptr : iqm,
+                    flat_type ? nullptr : qm_dist, txb_ctx, tx_type_cost, rate, entropy_ctx,
+                    stream);
 }

@@ -191,6 +191,69 @@ int lavish_av1_quant_batch(const int32_t *coeff, int nblocks, int tx_size,
                            const uint8_t *dc_only, int32_t *qcoeff, int32_t *dqcoeff,
                            uint16_t *eob, uint8_t *flags, void *stream);
 
+/* ---- quantization matrices (av1_quant with using_qmatrix) ----------------
+ * A matrix is a caller-supplied DEVICE table of n = av1_get_max_eob(tx_size)
+ * uint8 weights, raster-indexed like the reference's qm_ptr[rc]: a slice of
+ * the caller's copy of one [3344] level table (wt_matrix_ref / iwt_matrix_ref,
+ * av1/common/quant_common.c) at lavish_qm_table_offset(tx_size).  NULL is the
+ * flat level 15. */
+/* aom_get_qmlevel (av1/common/quant_common.h:57-59); host. */
+int lavish_qm_level(int qindex, int first, int last);
+/* Element offset, inside one [3344] level table, of the matrix of
+ * av1_get_adjusted_tx_size(tx_size) as av1_qm_init lays the sizes out
+ * (quant_common.c:283-309); the 64-point sizes return the offset of the size
+ * whose matrix they reuse.  -1 for a bad size; host. */
+int lavish_qm_table_offset(int tx_size);
+
+/* lavish_quantize_batch through the *_helper_c bodies (quantize_fp_helper_c /
+ * highbd_quantize_fp_helper_c, av1/encoder/av1_quantize.c:70-198;
+ * aom_[highbd_]quantize_b_helper_c, aom_dsp/quantize.c:108-169,261-316):
+ * qm / iqm (device, n entries) each nullable on its own.  bit_depth 8 / 10 /
+ * 12.  Returns 0 or negative on bad arguments, nothing launched. */
+int lavish_quantize_qm_batch(const int32_t *coeff, int n, int nblocks,
+                             const int16_t *scan, const int16_t *iscan,
+                             int log_scale, int bit_depth, int quant_kind,
+                             const LavishQuantParams *qp, const uint8_t *qm,
+                             const uint8_t *iqm, int32_t *qcoeff,
+                             int32_t *dqcoeff, uint16_t *eob, void *stream);
+
+/* lavish_av1_quant_batch with the block's matrices and an optional fused
+ * dist_block_tx_domain (tx_search.c:1073-1116).
+ *   qm / iqm : as av1_setup_qmatrix would hand them for a 2-D type; for
+ *              tx_type >= IDTX they are treated as NULL here (av1_get_qmatrix,
+ *              quant_common.c:249-275).  FP / B / SATD_GATE take the helper
+ *              bodies only when both are non-NULL (av1_quantize.c:272,344 and
+ *              the highbd facades) and write lavish_av1_quant_batch's bits
+ *              otherwise; DC weights with each pointer on its own
+ *              (quantize_dc, :374-405).
+ *   dist_mode: 0 none; 1 av1_block_error / av1_highbd_block_error; 2
+ *              use_qm_dist_metric: av1_block_error_qm (:1049-1071, no bd
+ *              shift) when the effective qm is non-NULL, else as 1.  1 and 2
+ *              write dist / sse [nblocks] (device int64), RIGHT_SIGNED_SHIFT
+ *              by (MAX_TX_SCALE - tx_scale) * 2 included.  SKIP mode leaves
+ *              qcoeff / dqcoeff / eob untouched and measures the dqcoeff found.
+ * Returns 0, or negative, nothing launched: -1 size / type, -2 depth, -3
+ * mode, -4 NULL pointer, -5 dist_mode, -6 dist / sse NULL with dist_mode > 0. */
+int lavish_av1_quant_qm_batch(const int32_t *coeff, int nblocks, int tx_size,
+                              int tx_type, int bit_depth,
+                              const LavishPlaneQuant *pq, int mode,
+                              int skip_trellis,
+                              unsigned coeff_opt_satd_threshold, int qstep,
+                              const uint8_t *dc_only, const uint8_t *qm,
+                              const uint8_t *iqm, int dist_mode,
+                              int32_t *qcoeff, int32_t *dqcoeff, uint16_t *eob,
+                              uint8_t *flags, int64_t *dist, int64_t *sse,
+                              void *stream);
+
+/* av1_block_error_qm (tx_search.c:1049-1071) for nblocks blocks of n words:
+ * sum over i of ((coeff[i] - dqcoeff[i]) * qmatrix[scan[i]])^2, rounded >> 10
+ * per term, into err [nblocks], and the same of coeff[i] into ssz (device
+ * int64; no shift applied).  qmatrix / scan: device, n entries. */
+int lavish_block_error_qm_batch(const int32_t *coeff, const int32_t *dqcoeff,
+                                int n, int nblocks, const uint8_t *qmatrix,
+                                const int16_t *scan, int64_t *err,
+                                int64_t *ssz, void *stream);
+
 /* ---- coefficient rate ---------------------------- */
 /* MACROBLOCK::coeff_costs, field for field (CoeffCosts, av1/encoder/block.h:
  * 172-211): LV_MAP_COEFF_COST per [txs_ctx][plane_type] and LV_MAP_EOB_COST
@@ -256,6 +319,21 @@ int lavish_optimize_b_batch(const LavishCoeffCosts *costs, const int32_t *tcoeff
                             int rdmult, int sharpness, const int16_t *dequant,
                             const LavishTxbCtx *txb_ctx, int tx_type_cost, int32_t *rate,
                             uint8_t *entropy_ctx, void *stream);
+
+/* lavish_optimize_b_batch with the block's matrices (device, n entries,
+ * raster): iqm weights get_dqv per coefficient (txb_rdopt_utils.h:39-46;
+ * NULL: flat); qm_dist is the matrix of get_coeff_dist under
+ * AOM_DIST_METRIC_QM_PSNR (:48-64; NULL: the default metric).  Both are
+ * treated as NULL for tx_type >= IDTX.  With both NULL the results are
+ * lavish_optimize_b_batch's. */
+int lavish_optimize_b_qm_batch(const LavishCoeffCosts *costs, const int32_t *tcoeff,
+                               int32_t *qcoeff, int32_t *dqcoeff, uint16_t *eob,
+                               int nblocks, int plane, int tx_size, int tx_type,
+                               int bit_depth, int is_inter, int rdmult, int sharpness,
+                               const int16_t *dequant, const uint8_t *iqm,
+                               const uint8_t *qm_dist, const LavishTxbCtx *txb_ctx,
+                               int tx_type_cost, int32_t *rate, uint8_t *entropy_ctx,
+                               void *stream);
 
 /* ---- pixel-domain batch kernels ----------------------------------------- */
 /* One job = one block.  Offsets are in ELEMENTS (u8 or u16 samples / int16
@@ -1555,6 +1633,16 @@ LAVISH_QUANT_PROTO(aom_highbd_quantize_b_hip)
 LAVISH_QUANT_PROTO(aom_highbd_quantize_b_32x32_hip)
 LAVISH_QUANT_PROTO(aom_highbd_quantize_b_64x64_hip)
 #undef LAVISH_QUANT_PROTO
+/* aom_quantize_b_helper (av1/common/av1_rtcd_defs.pl:346) */
+void aom_quantize_b_helper_hip(const int32_t *coeff_ptr, intptr_t n_coeffs,
+                               const int16_t *zbin_ptr, const int16_t *round_ptr,
+                               const int16_t *quant_ptr,
+                               const int16_t *quant_shift_ptr,
+                               int32_t *qcoeff_ptr, int32_t *dqcoeff_ptr,
+                               const int16_t *dequant_ptr, uint16_t *eob_ptr,
+                               const int16_t *scan, const int16_t *iscan,
+                               const uint8_t *qm_ptr, const uint8_t *iqm_ptr,
+                               const int log_scale);
 void av1_highbd_quantize_fp_hip(const int32_t *coeff_ptr, intptr_t count,
                                 const int16_t *zbin_ptr,
                                 const int16_t *round_ptr,
