@@ -35,7 +35,7 @@ def _tables(seed):
 
 
 @pytest.mark.parametrize("s,tmask", CASES)
-@pytest.mark.parametrize("bd", [10, 8])
+@pytest.mark.parametrize("bd", [10, 8, 12])
 def test_rdo_rate_vs_oracle(L, s, tmask, bd):
     import torch
     from lavish_dsp import txb
