@@ -266,58 +266,6 @@ __device__ __forceinline__ int cand_cost(const Ctx& c, const Regs<W, H, FORM>&, 
   return (FORM == kObmc && c.estimate) ? obmc_estimate_cost(c, row, col) : mv_cost(c, row, col);
 }
 
-// the same level one candidate at a time (the upsampled error): steps 0-3
-// the cardinal points, 4 the diagonal, 5-6 the row / column bias points, 7
-// the diagonal bias point
-template <int W, int H, int FORM>
-__device__ __forceinline__ void tree_level_seq(const Ctx& c, const Regs<W, H, FORM>& R, int lane,
-                                               int hstep, int iters, Best& b) {
-  const int tr = b.row, tc = b.col;
-  uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, before = 0;
-  int dr = 0, dc = 0, br = tr, bc = tc;
-#pragma unroll 1
-  for (int s = 0; s < 8; ++s) {
-    int r, cl;
-    if (s < 4) {
-      r = tr + (s == 2 ? -hstep : s == 3 ? hstep : 0);
-      cl = tc + (s == 0 ? -hstep : s == 1 ? hstep : 0);
-    } else if (s == 4) {
-      dr = c2 <= c3 ? -hstep : hstep;
-      dc = c0 <= c1 ? -hstep : hstep;
-      r = tr + dr;
-      cl = tc + dc;
-    } else if (s == 5) {
-      if (iters <= 1) break;
-      br = b.row;
-      bc = b.col;
-      if (br == tr && bc == tc) break;
-      if (tr == br) dr = -dr;
-      else if (tc == bc) dc = -dc;
-      before = b.besterr;
-      r = br + dr;
-      cl = bc;
-    } else if (s == 6) {
-      r = br;
-      cl = bc + dc;
-    } else {
-      if (b.besterr == before) break;
-      r = br + dr;
-      cl = bc + dc;
-    }
-    uint32_t cost = 0x7FFFFFFFu;  // INT_MAX
-    if (in_range(c, r, cl)) {
-      int sum = 0;
-      uint32_t sse = 0;
-      seg_err<W, H, true>(c, R, lane, r, cl, sum, sse);
-      cost = settle<W, H>(c, R, r, cl, sum, sse, b);
-    }
-    c0 = s == 0 ? cost : c0;
-    c1 = s == 1 ? cost : c1;
-    c2 = s == 2 ? cost : c2;
-    c3 = s == 3 ? cost : c3;
-  }
-}
-
 struct KArgs {
   const uint8_t* src;
   const uint8_t* ref;

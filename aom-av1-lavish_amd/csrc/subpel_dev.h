@@ -1,12 +1,14 @@
 // subpel_dev.h -- what the sub-pel search kernels share (subpel.hip: the
 // single-reference searches; subpel_comp.hip: the compound, masked and OBMC
 // ones; subpel_hbd.hip and subpel_comp_hbd.hip: the same two at high bit
-// depth, with the u16 window loads and the depth's variance they share):
+// depth, with the u16 window loads and the depth's variance they share;
+// subpel_up_hbd.hip: the high-bit-depth upsampled error):
 // the wave shape (Sp), the byte-window loads, the horizontal 8-tap
 // pass, the wave reduction, the kernel tables and the best-mv record; and
 // the search itself -- the mv part of a context (MvCtx, mv_cost, in_range),
 // the strictly-better update (settle), the centre error, the candidate
-// batches and tree levels (check_n, two_level, tree_level), the level
+// batches and tree levels (check_n, two_level, tree_level, and tree_level_seq
+// for the upsampled error, one candidate at a time), the level
 // driver, the record store and the host-side argument checks.  A kernel
 // keeps how a candidate's error is computed (its context's own fields, the
 // lane's invariant words, seg_err) and how a candidate is priced
@@ -19,8 +21,10 @@ namespace lavish {
 namespace {
 
 // [kind][phase][tap] (interp_kernels.h): 0 the 8-tap regular, 4 the 4-tap
-// regular kernels (av1_get_filter's USE_8_TAPS / USE_4_TAPS)
-__constant__ int16_t kUpK[6][16][8] = LAVISH_K8_INIT;
+// regular kernels (av1_get_filter's USE_8_TAPS / USE_4_TAPS), 3 the bilinear
+// ones (USE_2_TAPS); a row of 8 taps is 16 aligned bytes (subpel_up_hbd.hip
+// reads it as 4 dwords)
+alignas(16) __constant__ int16_t kUpK[6][16][8] = LAVISH_K8_INIT;
 
 __constant__ uint8_t kBil2t[8][2] = {{128, 0}, {112, 16}, {96, 32}, {80, 48},
                                      {64, 64}, {48, 80},  {32, 96}, {16, 112}};
@@ -338,6 +342,59 @@ __device__ void tree_level(const C& c, const R& r, int lane, int hstep, int iter
     const int row[1] = {br + dr};
     const int col[1] = {bc + dc};
     check_n<W, H, 1>(c, r, lane, row, col, b, d1);
+  }
+}
+
+// tree_level one candidate at a time (the upsampled error, which a kernel
+// supplies as seg_err<W, H, true>): steps 0-3
+// the cardinal points, 4 the diagonal, 5-6 the row / column bias points, 7
+// the diagonal bias point
+template <int W, int H, class C, class R_>
+__device__ __forceinline__ void tree_level_seq(const C& c, const R_& R, int lane, int hstep,
+                                               int iters, Best& b) {
+  const int tr = b.row, tc = b.col;
+  uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, before = 0;
+  int dr = 0, dc = 0, br = tr, bc = tc;
+#pragma unroll 1
+  for (int s = 0; s < 8; ++s) {
+    int r, cl;
+    if (s < 4) {
+      r = tr + (s == 2 ? -hstep : s == 3 ? hstep : 0);
+      cl = tc + (s == 0 ? -hstep : s == 1 ? hstep : 0);
+    } else if (s == 4) {
+      dr = c2 <= c3 ? -hstep : hstep;
+      dc = c0 <= c1 ? -hstep : hstep;
+      r = tr + dr;
+      cl = tc + dc;
+    } else if (s == 5) {
+      if (iters <= 1) break;
+      br = b.row;
+      bc = b.col;
+      if (br == tr && bc == tc) break;
+      if (tr == br) dr = -dr;
+      else if (tc == bc) dc = -dc;
+      before = b.besterr;
+      r = br + dr;
+      cl = bc;
+    } else if (s == 6) {
+      r = br;
+      cl = bc + dc;
+    } else {
+      if (b.besterr == before) break;
+      r = br + dr;
+      cl = bc + dc;
+    }
+    uint32_t cost = 0x7FFFFFFFu;  // INT_MAX
+    if (in_range(c, r, cl)) {
+      int sum = 0;
+      uint32_t sse = 0;
+      seg_err<W, H, true>(c, R, lane, r, cl, sum, sse);
+      cost = settle<W, H>(c, R, r, cl, sum, sse, b);
+    }
+    c0 = s == 0 ? cost : c0;
+    c1 = s == 1 ? cost : c1;
+    c2 = s == 2 ? cost : c2;
+    c3 = s == 3 ? cost : c3;
   }
 }
 

@@ -750,6 +750,10 @@ _lib.lavish_highbd_find_best_sub_pixel_tree_batch.argtypes = [
     _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32,
     ctypes.POINTER(MvCostParams), _vp, _vp, _vp]
 _lib.lavish_highbd_find_best_sub_pixel_tree_batch.restype = _i32
+_lib.lavish_highbd_find_best_sub_pixel_tree_batch_ex.argtypes = [
+    _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32,
+    ctypes.POINTER(MvCostParams), _vp, _vp, _vp]
+_lib.lavish_highbd_find_best_sub_pixel_tree_batch_ex.restype = _i32
 
 
 def _hbd_planes(src, ref):
@@ -788,11 +792,14 @@ def highbd_full_pixel_search_batch(src, ref, w, h, jobs, cost, bit_depth=10, met
 def highbd_find_best_sub_pixel_tree_batch(src, ref, w, h, jobs, cost, bit_depth=10,
                                           method="pruned_more", forced_stop=EIGHTH_PEL,
                                           allow_hp=False, iters_per_step=1, fullpel=None,
-                                          cost_lists=None, out=None, stream=None):
-    """lavish_highbd_find_best_sub_pixel_tree_batch:
-    find_best_sub_pixel_tree_batch (the bilinear error) over int16 / uint16
-    device planes holding `bit_depth`-bit pixels; fullpel / cost_lists: what
-    highbd_full_pixel_search_batch returned, still on the device."""
+                                          cost_lists=None, out=None, stream=None,
+                                          search_type=USE_2_TAPS_ORIG):
+    """lavish_highbd_find_best_sub_pixel_tree_batch_ex:
+    find_best_sub_pixel_tree_batch over int16 / uint16 device planes holding
+    `bit_depth`-bit pixels ("tree": the bilinear error with search_type
+    USE_2_TAPS_ORIG / USE_2_TAPS, aom_highbd_upsampled_pred's with USE_4_TAPS /
+    USE_8_TAPS; the pruned methods: the bilinear error); fullpel / cost_lists:
+    what highbd_full_pixel_search_batch returned, still on the device."""
     import torch
     _hbd_planes(src, ref)
     nj = jobs.numel() // SUBPEL_JOB_DTYPE.itemsize
@@ -801,12 +808,12 @@ def highbd_find_best_sub_pixel_tree_batch(src, ref, w, h, jobs, cost, bit_depth=
     if cost_lists is not None:
         assert cost_lists.dtype == torch.int32 and cost_lists.numel() >= 5 * nj
     out = _subpel_out(nj, out, src.device)
-    rc = _lib.lavish_highbd_find_best_sub_pixel_tree_batch(
+    rc = _lib.lavish_highbd_find_best_sub_pixel_tree_batch_ex(
         _vp(src.data_ptr()), src.stride(0), _vp(ref.data_ptr()), src.stride(0), w, h, bit_depth,
         _vp(jobs.data_ptr()), None if fullpel is None else _vp(fullpel.data_ptr()), nj,
-        SUBPEL_METHODS[method], forced_stop, int(allow_hp), iters_per_step, ctypes.byref(cost),
-        None if cost_lists is None else _vp(cost_lists.data_ptr()), _vp(out.data_ptr()),
-        _stream_ptr(stream))
+        SUBPEL_METHODS[method], search_type, forced_stop, int(allow_hp), iters_per_step,
+        ctypes.byref(cost), None if cost_lists is None else _vp(cost_lists.data_ptr()),
+        _vp(out.data_ptr()), _stream_ptr(stream))
     if rc != 0:
         raise ValueError("lavish_highbd_find_best_sub_pixel_tree_batch rejected its arguments "
                          "(rc=%d)" % rc)
@@ -834,6 +841,14 @@ _lib.lavish_highbd_obmc_find_best_sub_pixel_tree_batch.argtypes = [
     _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, ctypes.POINTER(MvCostParams),
     _vp, _vp, _vp, _vp]
 _lib.lavish_highbd_obmc_find_best_sub_pixel_tree_batch.restype = _i32
+_lib.lavish_highbd_comp_find_best_sub_pixel_tree_batch_ex.argtypes = [
+    _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+    ctypes.POINTER(MvCostParams), _vp, _vp, _i32, _vp, _vp]
+_lib.lavish_highbd_comp_find_best_sub_pixel_tree_batch_ex.restype = _i32
+_lib.lavish_highbd_obmc_find_best_sub_pixel_tree_batch_ex.argtypes = [
+    _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _i32,
+    ctypes.POINTER(MvCostParams), _vp, _vp, _vp, _vp]
+_lib.lavish_highbd_obmc_find_best_sub_pixel_tree_batch_ex.restype = _i32
 
 
 def _ptr16(t):
@@ -909,21 +924,24 @@ def highbd_comp_find_best_sub_pixel_tree_batch(src, ref, w, h, jobs, cost, secon
                                                mask_stride=0, bit_depth=10, method="pruned_more",
                                                forced_stop=EIGHTH_PEL, allow_hp=False,
                                                iters_per_step=1, fullpel=None, start_from=0,
-                                               out=None, stream=None):
-    """lavish_highbd_comp_find_best_sub_pixel_tree_batch:
-    comp_find_best_sub_pixel_tree_batch (the bilinear error) over int16 /
-    uint16 planes; fullpel: the bytes one of the highbd compound full-pel calls
-    returned, still on the device."""
+                                               out=None, stream=None,
+                                               search_type=USE_2_TAPS_ORIG):
+    """lavish_highbd_comp_find_best_sub_pixel_tree_batch_ex:
+    comp_find_best_sub_pixel_tree_batch over int16 / uint16 planes ("tree" with
+    a search_type other than USE_2_TAPS_ORIG: the error of
+    aom_highbd_comp_avg_upsampled_pred / _comp_mask_upsampled_pred, the centre
+    at the start itself; else the bilinear error); fullpel: the bytes one of
+    the highbd compound full-pel calls returned, still on the device."""
     import torch
     _hbd_planes(src, ref)
     nj = jobs.numel() // COMP_SUBPEL_JOB_DTYPE.itemsize
     if fullpel is not None:
         assert fullpel.numel() >= nj * COMP_RESULT_DTYPE.itemsize
     out = _subpel_out(nj, out, src.device)
-    rc = _lib.lavish_highbd_comp_find_best_sub_pixel_tree_batch(
+    rc = _lib.lavish_highbd_comp_find_best_sub_pixel_tree_batch_ex(
         _vp(src.data_ptr()), src.stride(0), _vp(ref.data_ptr()), src.stride(0), w, h, bit_depth,
         _vp(jobs.data_ptr()), None if fullpel is None else _vp(fullpel.data_ptr()), start_from,
-        nj, SUBPEL_METHODS[method], forced_stop, int(allow_hp), iters_per_step,
+        nj, SUBPEL_METHODS[method], search_type, forced_stop, int(allow_hp), iters_per_step,
         ctypes.byref(cost), _ptr16(second_pred), _ptr(mask, torch.uint8), mask_stride,
         _vp(out.data_ptr()), _stream_ptr(stream))
     if rc != 0:
@@ -935,19 +953,23 @@ def highbd_comp_find_best_sub_pixel_tree_batch(src, ref, w, h, jobs, cost, secon
 def highbd_obmc_find_best_sub_pixel_tree_batch(ref, ref_stride, w, h, jobs, cost, wsrc, obmc_mask,
                                                bit_depth=10, forced_stop=EIGHTH_PEL,
                                                allow_hp=False, iters_per_step=1, fullpel=None,
-                                               out=None, stream=None):
-    """lavish_highbd_obmc_find_best_sub_pixel_tree_batch:
-    obmc_find_best_sub_pixel_tree_batch with USE_2_TAPS_ORIG over int16 /
-    uint16 reference planes."""
+                                               out=None, stream=None,
+                                               search_type=USE_2_TAPS_ORIG):
+    """lavish_highbd_obmc_find_best_sub_pixel_tree_batch_ex:
+    obmc_find_best_sub_pixel_tree_batch over int16 / uint16 reference planes
+    (USE_2_TAPS_ORIG: osvf, the centre at mv (0, 0), no L1 cost types; the
+    other types: aom_highbd_upsampled_pred then ovf, the centre at the start,
+    any cost type)."""
     import torch
     _hbd_planes(ref, ref)
     nj = jobs.numel() // COMP_SUBPEL_JOB_DTYPE.itemsize
     if fullpel is not None:
         assert fullpel.numel() >= nj * COMP_RESULT_DTYPE.itemsize
     out = _subpel_out(nj, out, ref.device)
-    rc = _lib.lavish_highbd_obmc_find_best_sub_pixel_tree_batch(
+    rc = _lib.lavish_highbd_obmc_find_best_sub_pixel_tree_batch_ex(
         _vp(ref.data_ptr()), ref_stride, w, h, bit_depth, _vp(jobs.data_ptr()),
-        None if fullpel is None else _vp(fullpel.data_ptr()), nj, forced_stop, int(allow_hp),
+        None if fullpel is None else _vp(fullpel.data_ptr()), nj, search_type, forced_stop,
+        int(allow_hp),
         iters_per_step, ctypes.byref(cost), _ptr(wsrc, torch.int32),
         _ptr(obmc_mask, torch.int32), _vp(out.data_ptr()), _stream_ptr(stream))
     if rc != 0:

@@ -1249,6 +1249,28 @@ int lavish_highbd_find_best_sub_pixel_tree_batch(
     int forced_stop, int allow_hp, int iters_per_step,
     const LavishMvCostParams *cost, const int32_t *cost_lists,
     LavishSubpelResult *out, void *stream);
+/* The same with var_params.subpel_search_type (0 USE_2_TAPS_ORIG .. 3
+ * USE_8_TAPS; else -7), as lavish_find_best_sub_pixel_tree_batch_ex adds it to
+ * the 8-bit call (csrc/subpel_up_hbd.hip).  SUBPEL_TREE with USE_4_TAPS /
+ * USE_8_TAPS ranks by upsampled_pref_error's is_cur_buf_hbd branch
+ * (av1/encoder/mcomp.c:2428-2448): aom_highbd_upsampled_pred_c's prediction
+ * (av1/encoder/reconinter_enc.c:562-640, unscaled reference: every
+ * aom_highbd_convolve8 pass rounded by FILTER_BITS and clipped to
+ * (1 << bit_depth) - 1, the 2-D case's intermediate rows included), then the
+ * depth's vf; with USE_2_TAPS it equals the bilinear svf.  The pruned methods
+ * take the svf for every type.  Type 0 is the call above exactly.
+ * Padding with SUBPEL_TREE and USE_4_TAPS / USE_8_TAPS: for every mv inside
+ * the SubpelMvLimits the (w + 7) x (h + 7) elements that start 3 rows and 3
+ * elements before the mv's full-pel floor must address memory, plus one
+ * element before and after each row of that window (the horizontal pass loads
+ * the aligned dwords that contain its 11 pixels). */
+int lavish_highbd_find_best_sub_pixel_tree_batch_ex(
+    const uint16_t *src, int src_stride, const uint16_t *ref, int ref_stride,
+    int w, int h, int bit_depth, const LavishSubpelJob *jobs,
+    const LavishDiamondResult *fullpel, int njobs, int subpel_search_method,
+    int subpel_search_type, int forced_stop, int allow_hp, int iters_per_step,
+    const LavishMvCostParams *cost, const int32_t *cost_lists,
+    LavishSubpelResult *out, void *stream);
 
 /* The compound, masked and OBMC sub-pel searches (csrc/subpel_comp.hip),
  * 8-bit, unscaled reference, one wave per job: what follows
@@ -1334,9 +1356,10 @@ int lavish_obmc_find_best_sub_pixel_tree_batch(
  * uint8_t with mask_stride, wsrc / obmc_mask int32_t.  Everything else --
  * the searches, second_best_mv, fullpel chaining with start_from 0 / 1 and
  * its INT_MAX / -32768 record, the three OBMC sub-pel peculiarities -- is the
- * 8-bit twin's.  The sub-pel calls take no subpel_search_type: the error is
- * the bilinear one (USE_2_TAPS_ORIG), as in
- * lavish_highbd_find_best_sub_pixel_tree_batch.
+ * 8-bit twin's.  The sub-pel calls without subpel_search_type take the
+ * bilinear error (USE_2_TAPS_ORIG), as
+ * lavish_highbd_find_best_sub_pixel_tree_batch; their _ex forms below add the
+ * type.
  * Padding: as the 8-bit twins, in elements: exactly the w x h blocks (full
  * pel) or the (w + 1) x (h + 1) windows (sub pel) the reference reads.
  * Return codes are the twins', and a bit_depth outside {8, 10, 12} returns
@@ -1377,6 +1400,39 @@ int lavish_highbd_obmc_find_best_sub_pixel_tree_batch(
     const LavishCompSubpelJob *jobs, const LavishCompSearchResult *fullpel,
     int njobs, int forced_stop, int allow_hp, int iters_per_step,
     const LavishMvCostParams *cost, const int32_t *wsrc,
+    const int32_t *obmc_mask, LavishSubpelResult *out, void *stream);
+
+/* The two sub-pel calls above with var_params.subpel_search_type where the
+ * 8-bit twins have it (0 USE_2_TAPS_ORIG .. 3 USE_8_TAPS; else -7),
+ * csrc/subpel_up_hbd.hip.  Type 0, and the pruned methods at any type, are
+ * the calls above exactly.  SUBPEL_TREE with another type ranks by
+ * upsampled_pref_error's is_cur_buf_hbd branch: aom_highbd_upsampled_pred_c
+ * (USE_2_TAPS: the bilinear kernels of av1_get_filter through the same
+ * passes) combined as aom_highbd_comp_avg_upsampled_pred /
+ * aom_highbd_comp_mask_upsampled_pred, then the depth's vf, with the centre
+ * error read at the start mv itself (upsampled_setup_center_error).  OBMC
+ * with a type other than 0: upsampled_setup_obmc_center_error at the start,
+ * candidates priced by mv_err_cost_ (the L1 cost types are accepted), the
+ * error aom_highbd_upsampled_pred then ovf.  fullpel / start_from chaining,
+ * the try_second record and the return codes are the calls' above.
+ * Padding where the upsampled prediction runs: for every mv inside the
+ * SubpelMvLimits the (w + 7) x (h + 7) elements that start 3 rows and 3
+ * elements before the mv's full-pel floor, plus one element before and after
+ * each row of that window. */
+int lavish_highbd_comp_find_best_sub_pixel_tree_batch_ex(
+    const uint16_t *src, int src_stride, const uint16_t *ref, int ref_stride,
+    int w, int h, int bit_depth, const LavishCompSubpelJob *jobs,
+    const LavishCompSearchResult *fullpel, int start_from, int njobs,
+    int subpel_search_method, int subpel_search_type, int forced_stop,
+    int allow_hp, int iters_per_step, const LavishMvCostParams *cost,
+    const uint16_t *second_pred, const uint8_t *mask, int mask_stride,
+    LavishSubpelResult *out, void *stream);
+
+int lavish_highbd_obmc_find_best_sub_pixel_tree_batch_ex(
+    const uint16_t *ref, int ref_stride, int w, int h, int bit_depth,
+    const LavishCompSubpelJob *jobs, const LavishCompSearchResult *fullpel,
+    int njobs, int subpel_search_type, int forced_stop, int allow_hp,
+    int iters_per_step, const LavishMvCostParams *cost, const int32_t *wsrc,
     const int32_t *obmc_mask, LavishSubpelResult *out, void *stream);
 
 /* ---- Inter prediction -----------------------------
