@@ -2298,6 +2298,72 @@ void av1_upsample_intra_edge_hip(uint8_t *p, int sz);
 void av1_filter_intra_edge_high_hip(uint16_t *p, int sz, int strength);
 void av1_upsample_intra_edge_high_hip(uint16_t *p, int sz, int bd);
 
+/* ---- chroma from luma (UV_CFL_PRED) -----------------------------------------
+ * av1/common/cfl.c and the alpha estimate of cfl_pick_plane_parameter
+ * (av1/encoder/intra_mode_search.c:608-643), bit-exact.  Planes, AC cells and
+ * job tables are device memory; pixels are uint8_t (highbd 0, bit_depth 8) or
+ * uint16_t (highbd 1, bit_depth 8 / 10 / 12).  The transform sizes are the 14
+ * with both sides <= 32.  A job table is a plain int64_t [njobs][COLS] array,
+ * its columns named below.  An AC cell is the reference's ac_buf_q3: 32 x 32
+ * int16_t at CFL_BUF_LINE (32) stride, of which only the W x H corner of the
+ * chroma tx_size is written and read.  Every *_elems argument is the number of
+ * elements of its plane: a job whose tx_size, cell index or rectangle falls
+ * outside what the call declares is skipped on the device and writes nothing
+ * (validate on the host: lavish_dsp.cfl's builders do).  Asynchronous on
+ * `stream`.  Return 0, or negative: -1 null pointer, -5 bit depth / highbd,
+ * -6 subsampling (sub_x, sub_y) = (0, 1) or outside 0 .. 1 (the reference
+ * routes (0, 1) to its 4:4:4 function by accident of cfl_subsampling_lbd),
+ * -7 stride / element count.  njobs <= 0 is a no-op. */
+enum { LAVISH_CFL_AC_LUMA_OFF, LAVISH_CFL_AC_LUMA_W, LAVISH_CFL_AC_LUMA_H,
+       LAVISH_CFL_AC_TX_SIZE, LAVISH_CFL_AC_COLS };
+enum { LAVISH_CFL_PRED_CELL, LAVISH_CFL_PRED_DST_OFF, LAVISH_CFL_PRED_TX_SIZE,
+       LAVISH_CFL_PRED_ALPHA_Q3, LAVISH_CFL_PRED_COLS };
+enum { LAVISH_CFL_SEARCH_CELL, LAVISH_CFL_SEARCH_SRC_OFF, LAVISH_CFL_SEARCH_DC_OFF,
+       LAVISH_CFL_SEARCH_TX_SIZE, LAVISH_CFL_SEARCH_COLS };
+/* cfl_store (cfl.c:324-369) followed by cfl_compute_parameters (:177-185): job
+ * j subsamples the stored luma rectangle (element offset LUMA_OFF, LUMA_W x
+ * LUMA_H luma pixels, multiples of 4 up to 32, no larger after subsampling than
+ * the chroma TX_SIZE), pads it to the transform (cfl_pad), subtracts the
+ * rounded average and writes cell j of ac_cells. */
+int lavish_cfl_ac_batch(const void *luma, int luma_stride, int64_t luma_elems, int sub_x,
+                        int sub_y, const int64_t *jobs, int njobs, int16_t *ac_cells,
+                        int bit_depth, int highbd, void *stream);
+/* cfl_predict_lbd_c / cfl_predict_hbd_c (cfl.c:147-172) in place on dst, which
+ * holds the DC prediction on entry: dst = clip(dst + ROUND_POWER_OF_TWO_SIGNED(
+ * ALPHA_Q3 * ac, 6)), ALPHA_Q3 in -16 .. 16.  Many jobs may read one cell; the
+ * blocks of a call's jobs must not overlap. */
+int lavish_cfl_predict_batch(const int16_t *ac_cells, int64_t ncells, void *dst, int dst_stride,
+                             int64_t dst_elems, const int64_t *jobs, int njobs, int bit_depth,
+                             int highbd, void *stream);
+/* The fast leg of cfl_pick_plane_parameter for one chroma plane of a block per
+ * job: costs[j][idx], idx 0 .. 32, is aom_satd of the DCT_DCT forward 2-D
+ * transform of src - cfl prediction with alpha_q3 = idx - 16 on the DC
+ * prediction block at DC_OFF of dc (read, never written); est_idx[j] is the
+ * index the reference's walk ends on (up from 16 while the cost falls
+ * strictly, then down from 15 against the same running best).  One transform
+ * block per plane (the uv transform of a block <= 32x32 is the plane block). */
+int lavish_cfl_alpha_search_batch(const int16_t *ac_cells, int64_t ncells, const void *src,
+                                  int src_stride, int64_t src_elems, const void *dc,
+                                  int dc_stride, int64_t dc_elems, const int64_t *jobs,
+                                  int njobs, int32_t *costs, uint8_t *est_idx, int bit_depth,
+                                  int highbd, void *stream);
+/* Host: the two estimates as the block's parameters (intra_mode_search.c:
+ * 747-752, 802-804).  Returns 0 when both are CFL_INDEX_ZERO (16): no valid CfL
+ * mode, *alpha_idx = *joint_sign = 0; otherwise 1 with *alpha_idx =
+ * (cfl_alpha_u << 4) + cfl_alpha_v and *joint_sign = cfl_sign_u * CFL_SIGNS +
+ * cfl_sign_v - 1.  -1 for an estimate outside 0 .. 32. */
+int lavish_cfl_joint(int est_u, int est_v, uint8_t *alpha_idx, int8_t *joint_sign);
+/* Size-generic per-call forms on host buffers (the entries of
+ * lavish_dsp_cfl.h are these at the 14 sizes); width / height in {4, 8, 16,
+ * 32}, output_q3 / src / dst / ac_buf_q3 at CFL_BUF_LINE stride as in the
+ * reference.  cfl_luma_subsampling_{420,422,444}_{lbd,hbd}_c (width x height
+ * luma pixels in), subtract_average_c, cfl_predict_{lbd,hbd}_c. */
+void lavish_cfl_subsample_host(const void *input, int input_stride, uint16_t *output_q3,
+                               int width, int height, int sub_x, int sub_y, int highbd);
+void lavish_cfl_subtract_average_host(const uint16_t *src, int16_t *dst, int width, int height);
+void lavish_cfl_predict_host(const int16_t *ac_buf_q3, void *dst, int dst_stride, int alpha_q3,
+                             int bit_depth, int width, int height, int highbd);
+
 #ifdef __cplusplus
 }
 #endif
